@@ -8,7 +8,11 @@ already resident in HBM: BASELINE.json configs[1] = batch 8 per GPU of 16x224x22
 rank runs its own batch of 8; rank 0 broadcasts the weights once (RCCL) and gathers the maps every
 step.  Prints ONE JSON line on rank 0.
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the secondary figures after the
+timed steps: the pass with the post-process kernels, the latency of one batch alone, the eager-launch rate, the
+per-kernel roofline and the CPU baseline.  `--dump-outputs DIR` writes the maps of the last timed step to DIR.
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -22,6 +26,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+DUMP_BYTES = 60 << 20           # --dump-outputs: at most this many bytes of maps are written (under 64 MB with the header)
 
 
 def parse():
@@ -38,8 +43,8 @@ def parse():
     ap.add_argument("--wa", type=int, default=300, help="spectrogram columns (BASELINE: 300; reference default 111)")
     ap.add_argument("--no-graph", "--eager", dest="no_graph", action="store_true",
                     help="launch eagerly instead of replaying a hipGraph (the clip loop's default launch path)")
-    ap.add_argument("--no-eager-line", action="store_true", help="skip the short eager-launch measurement reported as `eager` beside "
-                    "the hipGraph number (single-GPU runs only)")
+    ap.add_argument("--no-eager-line", action="store_true", help="with --full: skip the short eager-launch measurement reported as "
+                    "`eager` beside the hipGraph number (single-GPU runs only)")
     ap.add_argument("--inflight", type=int, default=None, help="hipGraphs of the forward kept in flight (mspi_amd.runtime.GraphPipeline): "
                     "consecutive steps (batches) replay round-robin on this many streams, so the low-occupancy tail of one batch "
                     "overlaps the head of the next (each step is still one full forward of one batch; 1 = one batch at a time). "
@@ -54,11 +59,16 @@ def parse():
                     "to rehearse the multi-rank control flow on a box where the ranks have to share one GPU")
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous / barrier / max-over-ranks timing / JSON line with "
                     "NO GPU work (CPU test of the --gpus N launch path; the line says dry_run and carries no throughput)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-postproc", action="store_true", help="skip the second timed pass with the post-process kernel in the graph")
-    ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel timing table to stderr")
-    ap.add_argument("--kernel-detail", type=int, default=0, help="also print the N slowest individual launches")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the secondary figures: post-process "
+                    "pass, latency of one batch alone, eager-launch rate, per-kernel roofline, CPU baseline (each can be "
+                    "switched off below)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline")
+    ap.add_argument("--no-postproc", action="store_true", help="with --full: skip the second timed pass with the post-process kernel in the graph")
+    ap.add_argument("--kernel-table", action="store_true", help="with --full: print the per-kernel timing table to stderr")
+    ap.add_argument("--kernel-detail", type=int, default=0, help="with --full: also print the N slowest individual launches")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the saliency maps of the last timed step to "
+                    "DIR/saliency_maps.npy (float32; a fixed strided sample when they exceed %d MB)" % (DUMP_BYTES >> 20))
     return ap.parse_args()
 
 
@@ -194,6 +204,18 @@ def pmc_traffic(kname, model, B, S, wa):
     return {}
 
 
+def dump_outputs(path, maps):
+    """--dump-outputs: the maps as DIR/saliency_maps.npy, float32.  Beyond DUMP_BYTES the flattened maps are written as a
+    fixed strided sample (the form of the tests/golden fixtures), so the same arguments always select the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    a = maps.detach().float().cpu()
+    stride = -(-a.numel() * a.element_size() // DUMP_BYTES)
+    if stride > 1:
+        a = a.reshape(-1)[::stride]
+    np.save(os.path.join(path, "saliency_maps.npy"), a.numpy())
+
+
 def dry_run(args, rank, world):
     """The launch contract without a GPU: rendezvous, barrier, K empty steps, max over ranks, one JSON line."""
     multi = world > 1
@@ -265,7 +287,8 @@ def main():
         model = T.condition_(T.seeded(lambda: AudioVisualSaliencyModel(cfg), 0), name)
     finally:
         sys.stdout = so
-    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    cpu_leg = args.full and not multi and not args.no_cpu_baseline
+    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if cpu_leg else None
     model = model.to(dev)
     if multi:   # weight fan-out: one flat RCCL broadcast from rank 0 over xGMI
         from mspi_amd.sharding import broadcast_weights
@@ -306,6 +329,7 @@ def main():
     pending = [None]                              # staging slot whose maps still have to be collected
     comm_stream = torch.cuda.Stream() if pipe else torch.cuda.current_stream()
     counter = [0]
+    last = [0]                                    # the ticket of the latest replay: its slot holds the last step's maps
 
     def gather(o):
         if not multi or os.environ.get("MSPI_BENCH_NO_GATHER"):     # experiment switches: everything but the collective
@@ -344,12 +368,12 @@ def main():
             gather(o)
             return
         if not collecting:
-            pipe.submit()
+            last[0] = pipe.submit()
             return
         slot = i % NSLOT
         if collected[slot] is not None and not collected[slot].query():
             collected[slot].synchronize()         # host-side guard; with 4 slots it never actually waits
-        pipe.submit()
+        last[0] = pipe.submit()
         # the gather of the PREVIOUS batch is issued after this batch's replay is queued, so a collective that blocks the
         # host cannot drain the GPU between batches
         prev, pending[0] = pending[0], slot
@@ -391,13 +415,19 @@ def main():
         ok = ok and all(torch.equal(outs[0], o) for o in outs[1:])
     if not ok:
         raise SystemExit("bench: the saliency maps are not finite log-probability maps")
+    if args.dump_outputs and rank == 0:
+        if gathered is not None and args.backend == "nccl" and not os.environ.get("MSPI_BENCH_NO_GATHER"):
+            maps = torch.cat(gathered)            # what rank 0 receives: every rank's maps of the last step
+        else:
+            maps = pipe.fetch(last[0]) if pipe else outs[0]
+        dump_outputs(args.dump_outputs, maps)
 
     # SURVEY 8d metric (2): saliency-map ms/clip INCLUDING the post-process kernels (inference.py:72-91: blur, exp, resize to
     # 640x480, min-max, uint8) -- the same pipeline with mspi_postprocess_u8 captured behind the forward, timed the same way.
     pp = None
-    lat_main = round(pipe.latency_ms(), 4) if pipe else None
+    lat_main = round(pipe.latency_ms(), 4) if pipe and args.full else None
     layout_main = pipe.layout if pipe else None
-    if pipe and not args.no_postproc:
+    if pipe and args.full and not args.no_postproc:
         # the SAME pipeline (same graphs, same streams, same hardware queues) with the four post-process launches issued on
         # each replay's own stream right behind it: a second pipeline lands on other queues and measures the layout, not the
         # kernels (seen: +1.1 ms latency for 0.13 ms of kernels)
@@ -429,7 +459,7 @@ def main():
     # work: DESIGN.md section 3, profiles/r03_clip_loop_pipeline.txt), so its model rate is put on record beside the graph's:
     # the same forward, same resident inputs, launched call by call from Python on the three branch streams.
     eager = None
-    if pipe and not multi and not args.no_eager_line:
+    if pipe and args.full and not multi and not args.no_eager_line:
         ne = max(3, min(10, args.steps))
         for _ in range(2):
             model(clips, audio)
@@ -472,11 +502,11 @@ def main():
         line.update(pp)
     if eager:
         line["eager"] = eager
-    if graph_mode:   # latency of ONE batch alone on the chip (no neighbouring batch in flight): median of 7 replays
+    if graph_mode and args.full:   # latency of ONE batch alone on the chip (no neighbouring batch in flight): median of 7 replays
         line["latency_ms_per_batch"] = lat_main
         line["saliency_map_ms_per_clip"] = round((pp["latency_ms_per_batch_with_postproc"] if pp else line["latency_ms_per_batch"]) / B, 4)
 
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # per-launch HIP-event timing of every C-ABI call: eager, same inputs, ONE stream (the branch overlap is
         # switched off here so that each launch is timed alone on the chip, as rocprofv3's kernel trace does)
         from mspi_amd.model import model_utils as MU
@@ -531,7 +561,7 @@ def main():
         line["roofline"]["avg_launch_us"] = round(1e3 * d["ms"] / d["calls"], 3)
         line["roofline"]["share_of_step"] = round(d["ms"] / tot, 4)
 
-    if not multi and not args.no_cpu_baseline:
+    if cpu_leg:
         line["cpu_baseline"] = cpu_baseline(sd_cpu, cfg, name, clips.cpu(), audio.cpu())
 
     print(json.dumps(line))

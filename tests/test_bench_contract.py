@@ -1,4 +1,5 @@
-"""bench.py's one-line JSON contract (driver-facing): keys, types, roofline / cpu_baseline objects, the multi-rank switch."""
+"""bench.py's one-line JSON contract (driver-facing): keys, types, roofline / cpu_baseline objects (--full), --dump-outputs,
+the multi-rank switch."""
 import json
 import os
 import subprocess
@@ -59,7 +60,8 @@ def test_host_cores_respects_affinity():
 @pytest.mark.gpu
 def test_bench_line_schema(dev):
     env = dict(os.environ, MSPI_BENCH_CPU_BUDGET_S="4")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--stream-layouts", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--stream-layouts", "2",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -81,3 +83,54 @@ def test_bench_line_schema(dev):
     # SURVEY 8d metric (2): ms/clip including the post-process kernels, from the product's own launch path
     assert d["ms_per_clip_with_postproc"] >= 0.9 * d["ms_per_clip"] and d["saliency_map_ms_per_clip"] > 0
     assert "GraphPipeline" in d["config"]["launch"]
+
+
+def test_dump_outputs_writes_float32_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: the maps as float32 .npy; above the byte cap a fixed strided sample of the flattened maps."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    maps = torch.arange(2 * 5 * 7, dtype=torch.float32).reshape(2, 5, 7)
+    bench.dump_outputs(str(tmp_path / "whole"), maps)
+    a = np.load(tmp_path / "whole" / "saliency_maps.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, maps.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64)
+    bench.dump_outputs(str(tmp_path / "sample"), maps.double())
+    a = np.load(tmp_path / "sample" / "saliency_maps.npy")
+    assert a.dtype == np.float32 and a.nbytes <= 64 and np.array_equal(a, maps.numpy().reshape(-1)[::5])
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_maps(dev, tmp_path):
+    """A plain run prints the headline line only (the secondary figures are --full's), times exactly --steps steps, and
+    --dump-outputs writes the maps of the last timed step: the smoke() workload's model and the bench's seeded inputs,
+    checked against the oracle on the CPU."""
+    import numpy as np
+    import torch
+    from mspi_amd import testing as T
+    from mspi_amd.model.model_utils import AudioVisualSaliencyModel
+    from oracle import restate as R
+    size, B, wa = 64, 2, 111
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--stream-layouts", "1",
+                        "--size", str(size), "--batch", str(B), "--wa", str(wa), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600, env=_env())
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, "bench.py must print exactly one line on stdout"
+    d = json.loads(lines[0])
+    assert d["metric"] == "clips_per_sec" and d["unit"] == "clips/s" and d["higher_is_better"] is True and d["steps"] == 3
+    assert d["dtype"] and d["ms_per_step"] > 0 and abs(d["value"] - B * 1e3 / d["ms_per_step"]) < 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "eager", "ms_per_clip_with_postproc", "latency_ms_per_batch"):
+        assert k not in d, k
+    maps = np.load(tmp_path / "out" / "saliency_maps.npy")
+    assert maps.dtype == np.float32 and maps.shape == (B, size, size)
+    cfg = T.make_cfg("x3dl", num_aud_tokens=9 * ((wa + 31) // 32), num_vis_tokens=16 * (size // 32) ** 2)
+    sd = T.seeded(lambda: AudioVisualSaliencyModel(cfg), 0).state_dict()
+    clips, audio = T.synth_inputs(B, 16, size, size, Wa=wa, seed=100)
+    with torch.no_grad():
+        ref, _ = R.audio_visual_forward(sd, clips, audio, "x3dl", cfg.MODEL.LATERAL_BOOL, cfg.MODEL.LATERAL_STRIDE)
+    assert tuple(ref.shape) == maps.shape
+    err = np.abs(maps - ref.numpy()).max()
+    assert err < 1e-3, err
