@@ -147,6 +147,13 @@ int mspi_dwconv_fwd(const MspiDwConvDesc* d, const float* x, const float* w, con
                     float* y, float* pool /*NULL or [N][rows][C]*/, mspi_stream_t stream);
 /* partial-sum rows per sample that mspi_dwconv_fwd writes for this descriptor (-1: pooling unsupported) */
 int mspi_dwconv_pool_rows(const MspiDwConvDesc* d);
+/* Which kernel instantiation mspi_dwconv_fwd launches for this descriptor in this process (host only, no GPU call; the
+ * MSPI_DW_* switches are read once per process; the pool argument does not change the choice):
+ *   kind * 1000 + K * 100 + stride * 10 + SW
+ * kind 1 = LDS-staged (dw_lds_kernel<K, SW>, stride 1), 2 = register tile (dw_tile_kernel<K, stride, SW, 2>),
+ * 3 = strip (dw_strip_kernel<K, W stride, 4>), 4 = generic (dw_kernel: 4000); -1 = invalid descriptor.
+ * mspi_dwconv_fwd selects its kernel by this same function. */
+int mspi_dwconv_variant(const MspiDwConvDesc* d);
 
 /* Squeeze-excite gate: gate[n,c] = sigmoid(fc2(relu(fc1(inv_count * sum_r pool[n,r,:]))))
  * (SlowFast/resnet_helper.py:27-73).  w1 [F][C], b1 [F], w2 [C][F], b2 [C]. */
@@ -172,8 +179,10 @@ int mspi_layernorm_fwd(const float* x, int64_t ldx, int64_t sNx, float* y, int64
  * Fused multi-head attention (flash style, MFMA, online softmax, fp32 in / fp32 accumulate):
  *   o[b,h,i,:] = softmax_j( scale * q[b,h,i,:] . k[b,h,j,:] + biasT[h,j,i] + maskT[b % nmask,j,i] ) v[b,h,j,:] (+ res)
  * q/k/v/o (and res, with o's strides) are addressed as base + b*sB + h*sH + token*sT + d (d contiguous).
- * D = head dim of q/k, Dv = head dim of v/o; (D,Dv) in {(32,32),(64,64),(96,96),(128,128),(128,96),(160,96)}.
+ * D = head dim of q/k, Dv = head dim of v/o; (D,Dv) in {(32,32),(64,64),(96,96),(128,128),(128,96),(144,96),(160,96)}.
  * biasT / maskT (optional) are stored key-major ([.][Nk][Nq]).
+ * A non-finite stored output sets the status word (mspi_set_status_word), as the GEMM epilogues do; padded query rows and
+ * key tiles never do.
  * tok_idx (optional, [nwin][N] int32): windowed sequences -- sequence b is window b % nwin of sample b / nwin
  * (strides sB then address the SAMPLE) and its token t lives at row tok_idx[b % nwin][t] of that sample, for
  * q, k, v, res and o alike: Swin's cyclic shift, window partition, window reverse and un-shift
@@ -207,6 +216,15 @@ size_t mspi_attn_ws_bytes(const MspiAttnDesc* d);
 int mspi_attn_fwd_ws(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
                      const float* biasT, const float* maskT, const int32_t* tok_idx, float* o, void* workspace,
                      mspi_stream_t stream);
+/* Which kernels the attention launch for this descriptor runs in this process (host only, no GPU call; the MSPI_ATTN_*
+ * switches are read once per process): has_bias / has_mask / has_tok = the optional arguments are given, has_ws = the
+ * call is mspi_attn_fwd_ws (else mspi_attn_fwd).
+ *   kind * 10000000 + D * 10000 + Dv * 10 + (1 if the key split's merge pass runs)
+ * kind 1 = fp32 (attn_kernel<D, Dv>), 2 = f16x3 without planes (attn_f16x3_kernel<D, Dv>), 3 = f16x3 on prefetched
+ * planes (attn_f16x3_kernel<D, Dv, true, true>), 4 = the same without prefetch (<D, Dv, true, false>, MSPI_ATTN_PF=0),
+ * 5 = software pipeline (attn_pipe_kernel<D, Dv>); -1 = (D, Dv) or prec not instantiated.
+ * mspi_attn_fwd / mspi_attn_fwd_ws select their kernels by this same function. */
+int mspi_attn_variant(const MspiAttnDesc* d, int32_t has_bias, int32_t has_mask, int32_t has_tok, int32_t has_ws);
 
 /* MViTv2 decomposed relative positions folded into the attention contraction (backbones/MViT.py:905-997):
  *   qa[b,h,i,:] = [ scale*q_i | q_i.Rh[hq(i),0..kH) | q_i.Rw[wq(i),0..kW) | q_i.Rt[tq(i),0..kT) | 0 ]   (DA columns)

@@ -176,7 +176,7 @@ class MultiScaleBlock(HipModule):
         q, k, v = head_ln(q, pk["nq"]), head_ln(k, pk["nk"]), head_ln(v, pk["nv"])
         Rh, Rw, Rt, rel_gemm = self._rel(pk, q_thw, k_thw)
         o = E.mvit_attention(q, k, v, B, heads, hd, a.scale, q_thw, k_thw, Rh, Rw, Rt,
-                             rel_gemm=rel_gemm if REL_GEMM and E.DEFAULT_PREC == E.PREC_F16X3 else None)
+                             rel_gemm=rel_gemm if REL_GEMM and E.DEFAULT_PREC == E.PREC_F16X3 else None, slot=E.attn_slot(pk))
         skip = E.conv(xn, pk["skip"]) if "skip" in pk else x          # DIM_MUL_IN_ATT: proj(norm1(x)) (MViT.py:1414-1415)
         if self.pool_skip is not None:
             skip = E.maxpool(skip, self.kernel_skip, self.stride_skip, tuple(int(kk // 2) for kk in self.kernel_skip))

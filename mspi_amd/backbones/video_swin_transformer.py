@@ -140,7 +140,7 @@ class SwinTransformerBlock3D(HipModule):
             xn = E.layernorm_for_gemm(x, *pk["n1"], 1e-5, pk["qkv"])
             qkv = E.conv(xn, pk["qkv"])
             o = E.attention(qkv, x.N * nwin, N, a.num_heads, self.dim // a.num_heads, a.scale, biasT=biasT, maskT=maskT,
-                            tok_idx=tok_idx)
+                            tok_idx=tok_idx, slot=E.attn_slot(pk))
         else:
             # The reference zero-pads norm1(x) up to a multiple of the window (:240-246), so a padding token enters the
             # attention as qkv(0) = the qkv bias.  All padding tokens share ONE extra row per sample: row D*H*W of the
@@ -152,7 +152,7 @@ class SwinTransformerBlock3D(HipModule):
             E.layernorm(x, *pk["n1"], 1e-5, out=xn.tokens(0, x.T, x.H, x.W))
             qkv = E.conv(xn, pk["qkv"])
             o = E.attention(qkv, x.N * nwin, N, a.num_heads, self.dim // a.num_heads, a.scale, biasT=biasT, maskT=maskT,
-                            tok_idx=tok_idx, rows_per_sample=R + 1).tokens(0, x.T, x.H, x.W)
+                            tok_idx=tok_idx, rows_per_sample=R + 1, slot=E.attn_slot(pk)).tokens(0, x.T, x.H, x.W)
         x = E.conv(o, pk["proj"], res=x)
         return E.mlp_tail(x, pk["mlp"], pk["n2"], 1e-5, res=x)   # dim 96 / 192: one fused launch (mspi_mlp_fwd)
 

@@ -19,6 +19,10 @@ namespace mspi {
 
 typedef float v16f __attribute__((ext_vector_type(16)));
 
+__device__ __forceinline__ bool nonfinite4(const float4 v) {
+  return nonfinite(v.x) || nonfinite(v.y) || nonfinite(v.z) || nonfinite(v.w);
+}
+
 struct AttnArgs {
   const float* q;
   const float* k;
@@ -38,6 +42,7 @@ struct AttnArgs {
   // key split (gridDim.z > 1): slice z of the key tiles leaves its unnormalised O^T, running maximum and running sum here
   float* part_o;       // [z][B*Hh][Nq][DV]
   float* part_ml;      // [z][B*Hh][Nq][2]
+  int* status;         // range guard (common.h, report_nonfinite): set when a stored output is inf / NaN
 };
 
 // D = head dim of Q/K (the contraction of S), DV = head dim of V / O.  They differ for MViT, whose decomposed
@@ -165,9 +170,10 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs p) {
     }
   }
 
-  if (qok) {
+  if (qok) {      // padded query rows (q >= Nq) store nothing and are never flagged
     const float inv = 1.f / l_run;
     const long oo = (long)sample * p.o_sB + (long)h * p.o_sH + (long)qrow * p.o_sT;
+    bool bad = false;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -180,8 +186,10 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs p) {
           const float4 rr = *reinterpret_cast<const float4*>(p.res + oo + dd);
           o4.x += rr.x; o4.y += rr.y; o4.z += rr.z; o4.w += rr.w;
         }
+        bad |= nonfinite4(o4);
         *reinterpret_cast<float4*>(p.o + oo + dd) = o4;
       }
+    report_nonfinite(p.status, bad);
   }
 }
 
@@ -551,9 +559,10 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const AttnArgs p) {
     }
     return;
   }
-  if (qok) {
+  if (qok) {      // padded query rows (q >= Nq) store nothing and are never flagged
     const float inv = 1.f / (l_run * (PSC * VSC));
     const long oo = (long)sample * p.o_sB + (long)h * p.o_sH + (long)qrow * p.o_sT;
+    bool bad = false;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -565,8 +574,10 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const AttnArgs p) {
           const float4 rr = *reinterpret_cast<const float4*>(p.res + oo + dd);
           o4.x += rr.x; o4.y += rr.y; o4.z += rr.z; o4.w += rr.w;
         }
+        bad |= nonfinite4(o4);
         *reinterpret_cast<float4*>(p.o + oo + dd) = o4;
       }
+    report_nonfinite(p.status, bad);
   }
 }
 
@@ -798,9 +809,10 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnArgs p) {
     }
     return;
   }
-  if (qok) {
+  if (qok) {      // padded query rows (q >= Nq) store nothing and are never flagged
     const float inv = 1.f / (l_run * (PSC * VSC));
     const long oo = (long)b * p.o_sB + (long)h * p.o_sH + (long)q * p.o_sT;
+    bool bad = false;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -812,8 +824,10 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnArgs p) {
           const float4 rr = *reinterpret_cast<const float4*>(p.res + oo + dd);
           o4.x += rr.x; o4.y += rr.y; o4.z += rr.z; o4.w += rr.w;
         }
+        bad |= nonfinite4(o4);
         *reinterpret_cast<float4*>(p.o + oo + dd) = o4;
       }
+    report_nonfinite(p.status, bad);
   }
 }
 
@@ -846,6 +860,7 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(const AttnArgs p, int n
     const float4 rr = *reinterpret_cast<const float4*>(p.res + oo);
     o.x += rr.x; o.y += rr.y; o.z += rr.z; o.w += rr.w;
   }
+  report_nonfinite(p.status, nonfinite4(o));
   *reinterpret_cast<float4*>(p.o + oo) = o;
 }
 
@@ -1083,6 +1098,38 @@ extern "C" int mspi_attn_fwd_ws(const MspiAttnDesc* d, const float* q, const flo
   return attn_fwd_impl(d, q, k, v, res, biasT, maskT, tok_idx, o, workspace, stream);
 }
 
+static bool attn_pair_ok(int D, int Dv) {
+  switch (D * 1000 + Dv) {
+    case 32032: case 64064: case 96096: case 128128: case 128096: case 144096: case 160096: return true;
+    default: return false;
+  }
+}
+
+// The kernels of this launch (include/mspi_hip.h, mspi_attn_variant): kind * 10^7 + D * 10^4 + Dv * 10 + merge, kind 1 = fp32,
+// 2 = f16x3 without planes, 3 = f16x3 on prefetched planes, 4 = planes without prefetch, 5 = software pipeline; -1 = not
+// instantiated.  attn_fwd_impl switches on this code, so the query cannot drift from what runs.
+static int attn_select(const MspiAttnDesc* d, bool bias, bool mask, bool tok, bool ws) {
+  if ((d->prec != MSPI_PREC_F32 && d->prec != MSPI_PREC_F16X3) || !attn_pair_ok(d->D, d->Dv)) return -1;
+  const int pair = d->D * 10000 + d->Dv * 10;
+  if (d->prec == MSPI_PREC_F32) return 10000000 + pair;
+  if (!ws) return 20000000 + pair;
+  // next tile's planes fetched into registers under the current tile's MFMAs: same-box A/B on the MViTv2-S shapes 2.377 ->
+  // 2.244 ms per forward, better or equal on every shape.  MSPI_ATTN_PF=0 switches it off for an A/B.
+  static const char* pf_env = getenv("MSPI_ATTN_PF");
+  const bool pf = !(pf_env && pf_env[0] == '0');
+  // software-pipelined form (attn_pipe_kernel) wherever there is no bias, mask or token index; MSPI_ATTN_PIPE=0: off
+  static const char* pipe_env = getenv("MSPI_ATTN_PIPE");
+  const bool plain = !bias && !mask && !tok;
+  const bool pipe = pf && plain && !(pipe_env && pipe_env[0] == '0');
+  const int split = (pf && plain) ? attn_ksplit(d) : 1;
+  return (pipe ? 50000000 : pf ? 30000000 : 40000000) + pair + (split > 1 ? 1 : 0);
+}
+
+extern "C" int mspi_attn_variant(const MspiAttnDesc* d, int32_t has_bias, int32_t has_mask, int32_t has_tok, int32_t has_ws) {
+  MSPI_REQUIRE(d, "mspi_attn_variant: null descriptor");
+  return attn_select(d, has_bias != 0, has_mask != 0, has_tok != 0, has_ws != 0);
+}
+
 static int attn_fwd_impl(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
                          const float* biasT, const float* maskT, const int32_t* tok_idx, float* o, void* ws,
                          mspi_stream_t stream) {
@@ -1096,6 +1143,11 @@ static int attn_fwd_impl(const MspiAttnDesc* d, const float* q, const float* k, 
   MSPI_REQUIRE(!maskT || d->nmask > 0, "mspi_attn_fwd: mask needs nmask > 0");
   MSPI_REQUIRE(!tok_idx || (d->nwin > 0 && d->B % d->nwin == 0 && d->Nq == d->Nk),
                "mspi_attn_fwd: a token index needs nwin > 0, B %% nwin == 0 and Nq == Nk");
+  MSPI_REQUIRE(d->prec == MSPI_PREC_F32 || d->prec == MSPI_PREC_F16X3, "mspi_attn_fwd: prec = %d", d->prec);
+  const int variant = attn_select(d, biasT != nullptr, maskT != nullptr, tok_idx != nullptr, ws != nullptr);
+  MSPI_REQUIRE(variant > 0, "mspi_attn_fwd: (D=%d, Dv=%d) not in {(32,32),(64,64),(96,96),(128,128),(128,96),(144,96),(160,96)}",
+               d->D, d->Dv);
+  const int kind = variant / 10000000;
   AttnArgs a;
   a.q = q; a.k = k; a.v = v; a.res = res; a.biasT = biasT; a.maskT = maskT; a.tok_idx = tok_idx; a.o = o;
   a.B = d->B; a.Hh = d->Hh; a.Nq = d->Nq; a.Nk = d->Nk; a.nmask = d->nmask > 0 ? d->nmask : 1;
@@ -1106,23 +1158,17 @@ static int attn_fwd_impl(const MspiAttnDesc* d, const float* q, const float* k, 
   a.v_sB = d->v_sB; a.v_sH = d->v_sH; a.v_sT = d->v_sT;
   a.o_sB = d->o_sB; a.o_sH = d->o_sH; a.o_sT = d->o_sT;
   a.scale = d->scale;
+  a.status = g_status_word;
   dim3 grid((unsigned)((d->Nq + 127) / 128), (unsigned)(d->B * d->Hh));
   hipStream_t s = (hipStream_t)stream;
   const int key = d->D * 1000 + d->Dv;
-  if (d->prec == MSPI_PREC_F16X3 && ws) {
+  if (kind >= 3) {      // K / V planes in the workspace
     a.Nkp = (int)attn_nkp(d);
     a.kp = reinterpret_cast<_Float16*>(ws);
     a.vp = a.kp + (size_t)d->B * d->Hh * 2 * a.Nkp * d->D;
     const size_t img_k = (size_t)d->B * d->Hh * (a.Nkp / 32) * 2 * 32 * (size_t)(d->D + 8);   // halves of all K images
     dim3 pgrid((unsigned)(a.Nkp / 32), (unsigned)(d->B * d->Hh));
-    // next tile's planes fetched into registers under the current tile's MFMAs: same-box A/B on the MViTv2-S shapes 2.377 ->
-    // 2.244 ms per forward, better or equal on every shape.  MSPI_ATTN_PF=0 switches it off for an A/B.
-    static const char* pf_env = getenv("MSPI_ATTN_PF");
-    const bool pf = !(pf_env && pf_env[0] == '0');
-    // software-pipelined form (attn_pipe_kernel) wherever there is no bias, mask or token index; MSPI_ATTN_PIPE=0: off
-    static const char* pipe_env = getenv("MSPI_ATTN_PIPE");
-    const bool pipe = pf && !biasT && !maskT && !tok_idx && !(pipe_env && pipe_env[0] == '0');
-    const int split = (pf && !biasT && !maskT && !tok_idx) ? attn_ksplit(d) : 1;
+    const int split = (variant % 10) ? attn_ksplit(d) : 1;
     if (split > 1) {
       a.part_o = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(ws) + attn_planes_bytes(d));
       a.part_ml = a.part_o + (size_t)split * d->B * d->Hh * d->Nq * d->Dv;
@@ -1131,17 +1177,15 @@ static int attn_fwd_impl(const MspiAttnDesc* d, const float* q, const float* k, 
     const dim3 mgrid((unsigned)(((long)d->B * d->Hh * d->Nq * (d->Dv / 4) + 255) / 256));
 #define MSPI_ATTN_PL(DD, DVV)                                                                        \
   case DD * 1000 + DVV:                                                                              \
-    if (pipe) {                                                                                      \
+    if (kind == 5) {                                                                                 \
       a.vp = a.kp + img_k;                                                                           \
       hipLaunchKernelGGL((attn_kv_planes_kernel<DD, DVV, true>), pgrid, dim3(256), 0, s, a);         \
       hipLaunchKernelGGL((attn_pipe_kernel<DD, DVV>), grid, dim3(256), 0, s, a);                     \
-      if (split > 1) hipLaunchKernelGGL((attn_merge_kernel<DVV>), mgrid, dim3(256), 0, s, a, split); \
-      break;                                                                                         \
+    } else {                                                                                         \
+      hipLaunchKernelGGL((attn_kv_planes_kernel<DD, DVV>), pgrid, dim3(256), 0, s, a);               \
+      if (kind == 3) hipLaunchKernelGGL((attn_f16x3_kernel<DD, DVV, true, true>), grid, dim3(256), 0, s, a);  \
+      else hipLaunchKernelGGL((attn_f16x3_kernel<DD, DVV, true, false>), grid, dim3(256), 0, s, a);  \
     }                                                                                                \
-    hipLaunchKernelGGL((attn_kv_planes_kernel<DD, DVV>), pgrid, dim3(256), 0, s, a);                 \
-    if (false) hipLaunchKernelGGL((attn_pipe_kernel<DD, DVV>), grid, dim3(256), 0, s, a);           \
-    else if (pf) hipLaunchKernelGGL((attn_f16x3_kernel<DD, DVV, true, true>), grid, dim3(256), 0, s, a);  \
-    else hipLaunchKernelGGL((attn_f16x3_kernel<DD, DVV, true, false>), grid, dim3(256), 0, s, a);    \
     if (split > 1) hipLaunchKernelGGL((attn_merge_kernel<DVV>), mgrid, dim3(256), 0, s, a, split);   \
     break;
     switch (key) {
@@ -1153,7 +1197,7 @@ static int attn_fwd_impl(const MspiAttnDesc* d, const float* q, const float* k, 
 #undef MSPI_ATTN_PL
     return check_launch("mspi_attn_fwd_ws");
   }
-  if (d->prec == MSPI_PREC_F16X3) {
+  if (kind == 2) {
     switch (key) {
       case 32032: hipLaunchKernelGGL((attn_f16x3_kernel<32, 32>), grid, dim3(256), 0, s, a); break;
       case 64064: hipLaunchKernelGGL((attn_f16x3_kernel<64, 64>), grid, dim3(256), 0, s, a); break;
@@ -1168,7 +1212,6 @@ static int attn_fwd_impl(const MspiAttnDesc* d, const float* q, const float* k, 
     }
     return check_launch("mspi_attn_fwd");
   }
-  MSPI_REQUIRE(d->prec == MSPI_PREC_F32, "mspi_attn_fwd: prec = %d", d->prec);
   switch (key) {
     case 32032: hipLaunchKernelGGL((attn_kernel<32, 32>), grid, dim3(256), 0, s, a); break;
     case 64064: hipLaunchKernelGGL((attn_kernel<64, 64>), grid, dim3(256), 0, s, a); break;

@@ -574,6 +574,30 @@ static int strip_variant(const MspiDwConvDesc* d) {
   return -1;
 }
 
+// The kernel instantiation for this descriptor (include/mspi_hip.h, mspi_dwconv_variant): kind * 1000 + K * 100 + stride * 10
+// + SW, kind 1 = LDS-staged, 2 = register tile, 3 = strip, 4 = generic.  The launch below switches on this code, so the query
+// cannot drift from what runs.  lc / tc receive the geometry of the LDS / tile kernel when one of them is chosen.
+static int dw_select(const MspiDwConvDesc* d, LdsCfg& lc, TileCfg& tc) {
+  if (lds_cfg(d, lc)) return 1000 + lc.K * 100 + 10 + lc.SW;
+  if (tile_cfg(d, tc)) return 2000 + tc.K * 100 + tc.STR * 10 + tc.SW;
+  switch (strip_variant(d)) {
+    case 0: return 3314;
+    case 1: return 3324;
+    case 2: return 3714;
+    case 3: return 3514;
+    default: return 4000;
+  }
+}
+
+extern "C" int mspi_dwconv_variant(const MspiDwConvDesc* d) {
+  MSPI_REQUIRE(d, "mspi_dwconv_variant: null descriptor");
+  DwArgs a;
+  if (fill_args(d, a, "mspi_dwconv_variant")) return -1;
+  LdsCfg lc;
+  TileCfg tc;
+  return dw_select(d, lc, tc);
+}
+
 extern "C" int mspi_dwconv_fwd(const MspiDwConvDesc* d, const float* x, const float* w, const float* bias, float* y,
                                float* pool, mspi_stream_t stream) {
   MSPI_REQUIRE(d && x && w && y, "mspi_dwconv_fwd: null argument");
@@ -584,49 +608,49 @@ extern "C" int mspi_dwconv_fwd(const MspiDwConvDesc* d, const float* x, const fl
                "mspi_dwconv_fwd: pointers must be 16-B aligned");
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.pool = pool;
   hipStream_t s = (hipStream_t)stream;
-  const int strip = strip_variant(d);
-  MSPI_REQUIRE(!pool || strip >= 0, "mspi_dwconv_fwd: SE pooling needs a (k,3,3)/(k,5,5)/(k,7,7) kernel with W-stride 1 or 2");
+  MSPI_REQUIRE(!pool || strip_variant(d) >= 0, "mspi_dwconv_fwd: SE pooling needs a (k,3,3)/(k,5,5)/(k,7,7) kernel with W-stride 1 or 2");
   TileCfg tc;
   LdsCfg lc;
-  if (lds_cfg(d, lc)) {
+  const int variant = dw_select(d, lc, tc);
+  if (variant < 2000) {
     const dim3 grid((unsigned)lc.nblk, (unsigned)lc.G, (unsigned)a.N);
     const int RW = lc.nsw * lc.SW + lc.K - 1, RH = lc.TH + lc.K - 1;
     const float icg = 1.f / (float)lc.CG, irw = 1.f / (float)RW, irh = 1.f / (float)RH;
 #define MSPI_DWL(KK, SWW)                                                                                              \
-    do {                                                                                                               \
+    case 1000 + KK * 100 + 10 + SWW:                                                                                   \
       if (pool) hipLaunchKernelGGL((dw_lds_kernel<KK, SWW, true>), grid, dim3(256), lc.lds, s, a, lc.CG, lc.TT, lc.TH, lc.nsw, lc.nTh, lc.nTw, icg, irw, irh);  \
       else hipLaunchKernelGGL((dw_lds_kernel<KK, SWW, false>), grid, dim3(256), lc.lds, s, a, lc.CG, lc.TT, lc.TH, lc.nsw, lc.nTh, lc.nTw, icg, irw, irh);      \
-    } while (0)
-    if (lc.K == 3) { if (lc.SW == 7) MSPI_DWL(3, 7); else MSPI_DWL(3, 4); }
-    else if (lc.K == 5) { if (lc.SW == 7) MSPI_DWL(5, 7); else MSPI_DWL(5, 4); }
-    else { if (lc.SW == 7) MSPI_DWL(7, 7); else MSPI_DWL(7, 4); }
+      break;
+    switch (variant) {
+      MSPI_DWL(3, 7) MSPI_DWL(3, 4) MSPI_DWL(5, 7) MSPI_DWL(5, 4) MSPI_DWL(7, 7) MSPI_DWL(7, 4)
+      default: set_error("mspi_dwconv_fwd: no LDS-staged kernel for variant %d", variant); return MSPI_EINVAL;
+    }
 #undef MSPI_DWL
-  } else if (tile_cfg(d, tc)) {
+  } else if (variant < 3000) {
     const dim3 grid((unsigned)tc.nblk, (unsigned)tc.G, (unsigned)a.N);
     const size_t lds = ((size_t)a.kT * tc.K * tc.K * tc.CG + (pool ? 256 : 0)) * sizeof(float4);
 #define MSPI_DWT(KK, ST, SWW)                                                                                            \
-    do {                                                                                                                 \
+    case 2000 + KK * 100 + ST * 10 + SWW:                                                                                \
       if (pool) hipLaunchKernelGGL((dw_tile_kernel<KK, ST, SWW, 2, true>), grid, dim3(256), lds, s, a, tc.CG, tc.PB, tc.HS, tc.S);  \
       else hipLaunchKernelGGL((dw_tile_kernel<KK, ST, SWW, 2, false>), grid, dim3(256), lds, s, a, tc.CG, tc.PB, tc.HS, tc.S);      \
-    } while (0)
-    if (tc.K == 7) { if (tc.SW == 7) MSPI_DWT(7, 1, 7); else MSPI_DWT(7, 1, 4); }
-    else if (tc.STR == 1) { if (tc.SW == 7) MSPI_DWT(3, 1, 7); else MSPI_DWT(3, 1, 4); }
-    else { if (tc.SW == 7) MSPI_DWT(3, 2, 7); else MSPI_DWT(3, 2, 4); }
+      break;
+    switch (variant) {
+      MSPI_DWT(7, 1, 7) MSPI_DWT(7, 1, 4) MSPI_DWT(3, 1, 7) MSPI_DWT(3, 1, 4) MSPI_DWT(3, 2, 7) MSPI_DWT(3, 2, 4)
+      default: set_error("mspi_dwconv_fwd: no tile kernel for variant %d", variant); return MSPI_EINVAL;
+    }
 #undef MSPI_DWT
-  } else if (strip >= 0) {
+  } else if (variant < 4000) {
     const long S = (a.Wo + DW_SW - 1) / DW_SW;
     const long per = (long)a.To * a.Ho * S * a.CV;
     dim3 grid((unsigned)((per + 255) / 256), (unsigned)a.N);
 #define MSPI_DW_LAUNCH(KW, SWS)                                                                                  \
-    do {                                                                                                           \
+    case 3000 + KW * 100 + SWS * 10 + DW_SW:                                                                       \
       if (pool) hipLaunchKernelGGL((dw_strip_kernel<KW, SWS, DW_SW, true>), grid, dim3(256), 0, s, a);             \
       else hipLaunchKernelGGL((dw_strip_kernel<KW, SWS, DW_SW, false>), grid, dim3(256), 0, s, a);                 \
-    } while (0)
-    switch (strip) {
-      case 0: MSPI_DW_LAUNCH(3, 1); break;
-      case 1: MSPI_DW_LAUNCH(3, 2); break;
-      case 3: MSPI_DW_LAUNCH(5, 1); break;
-      default: MSPI_DW_LAUNCH(7, 1); break;
+      break;
+    switch (variant) {
+      MSPI_DW_LAUNCH(3, 1) MSPI_DW_LAUNCH(3, 2) MSPI_DW_LAUNCH(5, 1) MSPI_DW_LAUNCH(7, 1)
+      default: set_error("mspi_dwconv_fwd: no strip kernel for variant %d", variant); return MSPI_EINVAL;
     }
 #undef MSPI_DW_LAUNCH
   } else {
@@ -639,9 +663,10 @@ extern "C" int mspi_dwconv_fwd(const MspiDwConvDesc* d, const float* x, const fl
 extern "C" int mspi_dwconv_pool_rows(const MspiDwConvDesc* d) {
   if (!d || strip_variant(d) < 0) return -1;
   LdsCfg lc;
-  if (lds_cfg(d, lc)) return (int)lc.nblk;
   TileCfg tc;
-  if (tile_cfg(d, tc)) return (int)tc.nblk;
+  const int variant = dw_select(d, lc, tc);
+  if (variant < 2000) return (int)lc.nblk;
+  if (variant < 3000) return (int)tc.nblk;
   const long Wo = (d->W + 2 * d->padW - d->kW) / d->strW + 1;
   const long S = (Wo + DW_SW - 1) / DW_SW;
   const long per = (long)d->To * d->Ho * S * (d->C / 4);

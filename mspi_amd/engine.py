@@ -156,7 +156,7 @@ def _need_gpu(t):
 # are split as they are, which is exact to 2^-22 relative while 2^-5 <~ |x| < 65504 for the LARGEST entries of the tensor:
 # beyond 65504 the hi half is inf; far below, the lo half sinks into f16 subnormals (absolute error 2^-25 per element,
 # whatever its size).  Two safeguards:
-#  * RANGE GUARD (always on): the GEMM kernels store 1 into a pinned host word when a result is inf / NaN
+#  * RANGE GUARD (always on): the GEMM and attention kernels store 1 into a pinned host word when a result is inf / NaN
 #    (mspi_set_status_word); range_flag() / check_range() read it -- no device call, the caller synchronises first.
 #  * RANGE CHECK on first sight of a pack (the first, autotuning forward -- the same "first input is representative"
 #    contract as cudnn.benchmark upstream, inference.py:19): max|x| of the layer's input outside [2^-5, 2^15] moves THAT layer
@@ -172,7 +172,7 @@ def _register_status_word():
 
 
 def range_flag(reset=True):
-    """True when a GEMM kernel has produced a non-finite result since the last reset.  Host read of a pinned word: valid for
+    """True when a GEMM or attention kernel has produced a non-finite result since the last reset.  Host read of a pinned word: valid for
     launches the caller has synchronised with (an event / stream / device sync)."""
     w = _STATUS["word"]
     if w is None:
@@ -184,11 +184,12 @@ def range_flag(reset=True):
 
 
 def check_range(sync=True):
-    """Raise MspiError when an f16x3 GEMM has overflowed (or was fed non-finite data) since the last check."""
+    """Raise MspiError when an f16x3 GEMM or attention has overflowed (or was fed non-finite data) since the last check."""
     if sync and torch.cuda.is_available():
         torch.cuda.synchronize()
     if range_flag():
-        raise MspiError("a GEMM produced inf/NaN: an activation left the f16x3 range (|x| >= 65504) or the input was not finite; "
+        raise MspiError("a GEMM or attention produced inf/NaN: an activation left the f16x3 range (|x| >= 65504; attention: "
+                        "|q| >= 1023, |k|, |v| >= 4094) or the input was not finite; "
                         "let the first forward see representative data (engine.autotune(True): out-of-range layers move to the "
                         "fp32 path) or run with MSPI_GEMM_PREC=f32")
 
@@ -853,6 +854,11 @@ def _dw_desc(x, k, s, p, out_ld):
     return d
 
 
+def dwconv_variant(x, pk):
+    """The kernel instantiation dwconv(x, pk) launches in this process (mspi_dwconv_variant: host only, no GPU call)."""
+    return _lib.load().mspi_dwconv_variant(C.byref(_dw_desc(x, pk.k, pk.stride, pk.pad, x.ld)))
+
+
 def dwconv(x, pk, out=None, pool=False, act=None):
     """pool=True (X3D squeeze-excite): also returns the [N, rows, C] partial sums of the pre-activation output."""
     lib = _lib.load()
@@ -929,15 +935,17 @@ def layernorm(x, gamma, beta, eps, out=None, act=ACT_NONE, table=None, sp=False)
     return out
 
 
-def attention(qkv, B, Ntok, heads, hd, scale, out=None, biasT=None, maskT=None, tok_idx=None, rows_per_sample=None):
+def attention(qkv, B, Ntok, heads, hd, scale, out=None, biasT=None, maskT=None, tok_idx=None, rows_per_sample=None, slot=None):
     """qkv: CL with rows (b, token) and 3*heads*hd columns laid out [3][heads][hd]
     (what `qkv.reshape(B,N,3,h,hd)` means, model/model_utils.py:100).  B sequences of Ntok tokens.
     biasT [heads][Ntok][Ntok] / maskT [nmask][Ntok][Ntok]: key-major additive terms (Swin).
     tok_idx int32 [nwin][Ntok]: the B = samples*nwin sequences are windows whose token t sits at row
     tok_idx[win][t] of its sample (shifted-window attention without gather/scatter passes).
     rows_per_sample: rows of qkv (and of the output) per sample when that is not nwin*Ntok -- Swin on a grid that is
-    not a multiple of the window keeps ONE extra row per sample for all padding tokens (tok_idx points there)."""
+    not a multiple of the window keeps ONE extra row per sample for all padding tokens (tok_idx points there).
+    slot: the calling layer's dict of precision decisions (see _attn_prec); None = the shape-keyed process-wide table."""
     lib = _lib.load()
+    _need_gpu(qkv.buf)
     Cc = heads * hd
     assert qkv.C == 3 * Cc and qkv.dense and (rows_per_sample is not None or qkv.M == B * Ntok)
     if out is None:
@@ -954,7 +962,7 @@ def attention(qkv, B, Ntok, heads, hd, scale, out=None, biasT=None, maskT=None, 
     d.o_sB, d.o_sH, d.o_sT = rows_per_sample * out.ld, hd, out.ld
     d.scale = float(scale)
     d.prec = _attn_prec(("qkv", heads, hd, Ntok, d.nwin), lambda: qkv.as_rows()[:, :Cc].abs().max() * abs(float(scale)),
-                        lambda: qkv.as_rows()[:, Cc:].abs().max())
+                        lambda: qkv.as_rows()[:, Cc:].abs().max(), slot)
     base = qkv.ptr
     with _Timed("attention", 4.0 * B * heads * Ntok * Ntok * hd, 16.0 * B * Ntok * Cc, "B=%d h=%d N=%d d=%d" % (B, heads, Ntok, hd)):
         _attn_launch(lib, d, base, base + 4 * Cc, base + 8 * Cc, None,
@@ -965,28 +973,45 @@ def attention(qkv, B, Ntok, heads, hd, scale, out=None, biasT=None, maskT=None, 
 
 ATTN_PLANES = _os.environ.get("MSPI_ATTN_PLANES", "1") != "0"      # A/B switch: K / V split once per head (mspi_attn_fwd_ws)
 # f16x3 attention scales q by 64 and k, v by 16 before the split (csrc/attn.hip): |q * scale| >= 1023 or |k|, |v| >= 4094 is inf
-# in the hi half.  First sight of an attention shape while tuning: operands beyond a quarter of that move the SHAPE to the fp32
-# MFMA kernel for good (same contract as the GEMM packs' range check).
+# in the hi half.  First sight of an attention LAYER (per shape) while tuning: operands beyond a quarter of that move that
+# layer's shape to the fp32 MFMA kernel for good (same contract as the GEMM packs' range check).  The decision lives in the
+# `slot` dict the module passes from its packed plan (pk["attn_prec"]), so every layer is checked on its own data and a
+# weight reload or .to() (HipModule._invalidate) checks again.  ATTN_PREC: the shape-keyed table of callers without a slot.
 ATTN_PREC = {}
+LAST_ATTN = [None]      # (descriptor, has_bias, has_mask, has_tok, has_ws) of the last attention launch: attn_variant()
 
 
-def _attn_prec(key, amax_q, amax_kv):
+def attn_slot(pk):
+    """The per-layer precision slot kept in a module's packed plan `pk` (rebuilt with it)."""
+    return pk.setdefault("attn_prec", {})
+
+
+def _attn_prec(key, amax_q, amax_kv, slot=None):
     if DEFAULT_PREC != PREC_F16X3:
         return DEFAULT_PREC
-    prec = ATTN_PREC.get(key)
+    table = ATTN_PREC if slot is None else slot
+    prec = table.get(key)
     if prec is None:
         if not _tuning():
             return PREC_F16X3
         aq, akv = float(amax_q()), float(amax_kv())
         bad = not (aq == aq and akv == akv) or aq >= 256.0 or akv >= 1024.0
-        prec = ATTN_PREC[key] = PREC_F32 if bad else PREC_F16X3
+        prec = table[key] = PREC_F32 if bad else PREC_F16X3
         if bad:
             RANGE_CHECK["moved"].append(("attention %s" % (key,), max(aq, akv)))
     return prec
 
 
+def attn_variant():
+    """The kernels of the last attention launch (mspi_attn_variant: host only, no GPU call); None before the first."""
+    if LAST_ATTN[0] is None:
+        return None
+    return _lib.load().mspi_attn_variant(C.byref(LAST_ATTN[0][0]), *LAST_ATTN[0][1:])
+
+
 def _attn_launch(lib, d, q, k, v, res, biasT, maskT, tok_idx, o, dev):
     nbytes = lib.mspi_attn_ws_bytes(C.byref(d)) if ATTN_PLANES else 0
+    LAST_ATTN[0] = (d, biasT is not None, maskT is not None, tok_idx is not None, nbytes > 0)
     if nbytes:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # stream-ordered: safe to drop after the launch
         check(lib.mspi_attn_fwd_ws(C.byref(d), q, k, v, res, biasT, maskT, tok_idx, o, ws.data_ptr(), _stream()), "mspi_attn_fwd_ws")
@@ -1074,14 +1099,16 @@ def space_to_depth(x, out=None):
     return out
 
 
-def mvit_attention(q, k, v, B, heads, hd, scale, q_thw, k_thw, Rh, Rw, Rt, out=None, rel_gemm=None):
+def mvit_attention(q, k, v, B, heads, hd, scale, q_thw, k_thw, Rh, Rw, Rt, out=None, rel_gemm=None, slot=None):
     """MViTv2 pooled attention with decomposed relative positions and residual pooling (backbones/MViT.py:1261-1301).
     q: CL rows (b, tq,hq,wq) x heads*hd (pooled + normed); k, v likewise over the pooled key grid.
     Rh / Rw / Rt: gathered tables [q_size][k_size][hd].  rel_gemm = (packed_tables, idx_h, idx_w, idx_t): the q . R dot
     products as ONE thin GEMM of the q rows against all distinct table rows (pack_conv of their stack) followed by a gather
     (mspi_mvit_qk_augment_p) instead of the per-(row, j) dot-product kernel.
+    slot: the calling layer's dict of precision decisions (see _attn_prec).
     Returns CL rows (b, q token) x heads*hd = softmax(...) v + q."""
     lib = _lib.load()
+    _need_gpu(q.buf)
     Nq, Nk = q_thw[0] * q_thw[1] * q_thw[2], k_thw[0] * k_thw[1] * k_thw[2]
     J = k_thw[0] + k_thw[1] + k_thw[2]
     DA = 128 if hd + J <= 128 else (144 if hd + J <= 144 else 160)      # k16 steps of S: 8 / 9 / 10
@@ -1115,7 +1142,8 @@ def mvit_attention(q, k, v, B, heads, hd, scale, q_thw, k_thw, Rh, Rw, Rt, out=N
     d.v_sB, d.v_sH, d.v_sT = Nk * v.ld, hd, v.ld
     d.o_sB, d.o_sH, d.o_sT = Nq * out.ld, hd, out.ld
     d.scale = 1.0
-    d.prec = _attn_prec(("mvit", heads, hd, Nq, Nk), lambda: qa.abs().max(), lambda: torch.maximum(ka.abs().max(), v.buf.abs().max()))
+    d.prec = _attn_prec(("mvit", heads, hd, Nq, Nk), lambda: qa.abs().max(), lambda: torch.maximum(ka.abs().max(), v.buf.abs().max()),
+                        slot)
     assert q.ld == out.ld and q.dense and out.dense   # residual pooling reads q with o's strides
     with _Timed("attention", 2.0 * B * heads * Nq * Nk * (DA + hd), 4.0 * B * heads * (Nq * (DA + 2 * hd) + Nk * (DA + hd)),
                 "B=%d h=%d Nq=%d Nk=%d d=%d+%d" % (B, heads, Nq, Nk, DA, hd)):

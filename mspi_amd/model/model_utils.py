@@ -79,7 +79,8 @@ class Block(HipModule):
         pk = self.pk
         dim = self.norm1.normalized_shape[0]
         h = E.layernorm_for_gemm(x, *pk["n1"], 1e-5, pk["qkv"])
-        o = E.attention(E.conv(h, pk["qkv"]), B, R, self.attn.num_heads, dim // self.attn.num_heads, self.attn.scale)
+        o = E.attention(E.conv(h, pk["qkv"]), B, R, self.attn.num_heads, dim // self.attn.num_heads, self.attn.scale,
+                        slot=E.attn_slot(pk))
         x = E.conv(o, pk["proj"], res=x)
         return E.mlp_tail(x, ("split", pk["fc1"], pk["fc2"]), pk["n2"], 1e-5, res=x)
 
