@@ -72,7 +72,7 @@ int mspi_device_count(void);
  *   :439-440 (lateral), :490-503 (readout); backbones/MViT.py:1059-1061;
  *   backbones/video_swin_transformer.py:151-153,449.
  * The input is addressed through element strides so NCDHW user tensors (clips, audio)
- * are consumed without a layout pass.  `gate` (optional, 1x1x1 stride-1 only) applies the
+ * are consumed without a layout pass.  `gate` (optional, 1x1x1 stride-1 unpadded only) applies the
  * X3D squeeze-excite scale and Swish to A on the fly:
  *   A'[m,k] = swish(A[m,k] * gate[n(m), k])      (SlowFast/resnet_helper.py:66-73,76-103)
  * ------------------------------------------------------------------------------------ */
@@ -116,6 +116,16 @@ int mspi_conv_fwd(const MspiConvDesc* d, const float* x, const float* w, const f
 size_t mspi_conv_splitk_ws_bytes(const MspiConvDesc* d, int32_t ksplit);
 int mspi_conv_splitk_fwd(const MspiConvDesc* d, const float* x, const float* w, const float* bias, const float* res,
                          float* y, void* workspace, int32_t ksplit, mspi_stream_t stream);
+/* Which kernel instantiation mspi_conv_fwd (ksplit <= 1) or mspi_conv_splitk_fwd (ksplit >= 2) launches for this descriptor,
+ * input pointer and gate pointer in this process (host only, no GPU call, no pointer dereferenced: x and gate are looked at
+ * for NULL and 16-B alignment, a NULL x is refused; the MSPI_CONV_* switches are read once per process):
+ *   kind * 10000000 + BM * 10000 + BN * 10 + form
+ * kind 1 = register-staged, 4 waves (tiles 0..3), 2 = register-staged, 8 waves (tiles 4, 5), 3 = split-K (64 x 64 tiles),
+ * 4 = LDS-DMA, 128 rows (tiles 6..11), 5 = LDS-DMA, 256 rows (tiles 12..14); form = 2 * (scalar gather) + prec for
+ * kinds 1..3, 0 = generic gather / 1 = dense (1x1x1, stride 1, no padding) / 2 = dense with the gate for kinds 4 and 5.
+ * -1 = a descriptor the launch refuses (mspi_last_error() says why).  The launches select their kernel by this same
+ * function; the weight, output and residual pointers are checked at launch only. */
+int mspi_conv_variant(const MspiConvDesc* d, const float* x, const float* gate, int32_t ksplit);
 
 /* Which kernel instantiation the calling thread's last mspi_conv_fwd launched:
  * (BM << 16) | (BN << 4) | (8 if 8 waves) | (4 if LDS-DMA staging) | (prec << 1) | (1 if scalar gather, 0 if
@@ -274,6 +284,10 @@ int mspi_x3d_ab_pool_rows(const MspiX3dAbDesc* d);
 size_t mspi_x3d_ab_packed_bytes(int32_t Cin, int32_t Cmid);
 int mspi_x3d_ab_fwd(const MspiX3dAbDesc* d, const void* x, const void* wa_packed, const void* bias_a, const void* wb,
                     const void* bias_b, void* u, void* pool /*or NULL*/, mspi_stream_t stream);
+/* Which instantiation mspi_x3d_ab_fwd launches (host only; pool does not change it): x3d_ab_kernel<KS, TH, TW, SL> as
+ * KS * 10000 + TH * 1000 + TW * 10 + SL (KS = ceil(Cin / 32), 7 x 14 tiles when W % 14 == 0, else 7 x 7); -1 = a
+ * descriptor the launch refuses.  mspi_x3d_ab_fwd selects by this function. */
+int mspi_x3d_ab_variant(const MspiX3dAbDesc* d);
 
 /* ------------------------------------------------------------------------------------
  * Max pooling, channels-last, -inf padding.
@@ -350,6 +364,9 @@ typedef struct {
 size_t mspi_mlp_packed_bytes(int32_t C, int32_t hidden);
 int mspi_mlp_fwd(const MspiMlpDesc* d, const void* x, const void* gamma, const void* beta, const void* w_packed,
                  const void* b1, const void* b2, const void* res, void* y, mspi_stream_t stream);
+/* Which instantiation mspi_mlp_fwd launches (host only; MSPI_MLP_TM is read once per process): mlp_fused_kernel<C, TM, NS, NWV>
+ * as C * 1000 + TM * 100 + NS * 10 + NWV; -1 = a descriptor the launch refuses.  mspi_mlp_fwd selects by this function. */
+int mspi_mlp_variant(const MspiMlpDesc* d);
 
 /* ------------------------------------------------------------------------------------
  * Row-stationary thin GEMM (1x1x1 conv / Linear with K <= 224 and few output columns):
@@ -374,6 +391,9 @@ size_t mspi_rowgemm_packed_bytes(int32_t K, int32_t N);
 int mspi_rowgemm_supported(int32_t K, int32_t N);
 int mspi_rowgemm_fwd(const MspiRowGemmDesc* d, const void* x, const void* w_packed, const void* bias, const void* res,
                      const void* gate, void* y, mspi_stream_t stream);
+/* Which instantiation mspi_rowgemm_fwd launches (host only): rowgemm_kernel<KSB, GATE> as KSB * 10 + GATE, has_gate = a gate
+ * is given; -1 = a descriptor the launch refuses.  mspi_rowgemm_fwd selects by this function. */
+int mspi_rowgemm_variant(const MspiRowGemmDesc* d, int32_t has_gate);
 
 /* ------------------------------------------------------------------------------------
  * X3D block seam, one launch for the end of block i and the start of block i+1 of a stage (csrc/mlp_fused.hip):
@@ -397,6 +417,9 @@ size_t mspi_x3d_ca_packed_bytes(int32_t D, int32_t Cx);
 int mspi_x3d_ca_supported(int32_t D, int32_t Cx);
 int mspi_x3d_ca_fwd(const MspiX3dCaDesc* d, const void* u, const void* gate, const void* w_packed, const void* bc,
                     const void* ba, const void* res, void* y, void* t, mspi_stream_t stream);
+/* Which instantiation mspi_x3d_ca_fwd launches (host only): x3d_ca_kernel<C, GATE> as C * 10 + GATE (C = D padded to 128 or
+ * 224), has_gate = a gate is given; -1 = a descriptor the launch refuses.  mspi_x3d_ca_fwd selects by this function. */
+int mspi_x3d_ca_variant(const MspiX3dCaDesc* d, int32_t has_gate);
 
 /* Saliency metrics (utils/compute_saliency_metrics.py:9-108; the terms of utils/loss.py:26-49): per sample n,
  * out[n] = { KL(gt || pred), CC(pred, gt), SIM(pred, gt), NSS(pred, fix) } over the L = H*W values of each map.
@@ -465,6 +488,11 @@ int mspi_join_planes_fwd(const void* planes, int64_t ldi, int64_t plane, int64_t
 int mspi_gemm_sp_fwd(const MspiConvDesc* d, const void* x_planes, int64_t ldx, int64_t xplane, const float* w,
                      const float* bias, const float* res, float* y, void* y_planes, int64_t ldys, int64_t yplane,
                      mspi_stream_t stream);
+/* Which instantiation mspi_gemm_sp_fwd launches for this descriptor (host only; y_planes is looked at for NULL only):
+ *   kind * 10000000 + BM * 10000 + BN * 10 + form,  kind 6 = 128 rows / 4 waves, 7 = 256 rows / 8 waves,
+ * form 0 = fp32 rows out, 1 = blocked planes out; -1 = a descriptor the launch refuses (mspi_last_error() says why).
+ * mspi_gemm_sp_fwd selects by this function; the plane strides are checked at launch only. */
+int mspi_gemm_sp_variant(const MspiConvDesc* d, const void* y_planes);
 
 /* y = a + b over n floats (plain residual add where no producer can fuse it). */
 int mspi_add(const float* a, const float* b, float* y, int64_t n, mspi_stream_t stream);

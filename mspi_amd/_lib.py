@@ -117,6 +117,7 @@ _SIGNATURES = {
     "mspi_conv_splitk_ws_bytes": (C.c_size_t, [C.POINTER(ConvDesc), C.c_int32]),
     "mspi_conv_splitk_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "mspi_conv_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
+    "mspi_conv_variant": (C.c_int, [C.POINTER(ConvDesc), _P, _P, C.c_int32]),
     "mspi_dwconv_fwd": (C.c_int, [C.POINTER(DwConvDesc), _P, _P, _P, _P, _P, _P]),
     "mspi_dwconv_pool_rows": (C.c_int, [C.POINTER(DwConvDesc)]),
     "mspi_dwconv_variant": (C.c_int, [C.POINTER(DwConvDesc)]),
@@ -150,19 +151,24 @@ _SIGNATURES = {
     "mspi_split_planes_fwd": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P]),
     "mspi_join_planes_fwd": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
     "mspi_gemm_sp_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P]),
+    "mspi_gemm_sp_variant": (C.c_int, [C.POINTER(ConvDesc), _P]),
     "mspi_saliency_metrics": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mspi_rowgemm_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mspi_rowgemm_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "mspi_rowgemm_fwd": (C.c_int, [C.POINTER(RowGemmDesc), _P, _P, _P, _P, _P, _P, _P]),
+    "mspi_rowgemm_variant": (C.c_int, [C.POINTER(RowGemmDesc), C.c_int32]),
     "mspi_x3d_ca_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mspi_x3d_ca_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "mspi_x3d_ca_fwd": (C.c_int, [C.POINTER(X3dCaDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mspi_x3d_ca_variant": (C.c_int, [C.POINTER(X3dCaDesc), C.c_int32]),
     "mspi_x3d_ab_supported": (C.c_int, [C.POINTER(X3dAbDesc)]),
     "mspi_x3d_ab_pool_rows": (C.c_int, [C.POINTER(X3dAbDesc)]),
     "mspi_x3d_ab_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mspi_x3d_ab_fwd": (C.c_int, [C.POINTER(X3dAbDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mspi_x3d_ab_variant": (C.c_int, [C.POINTER(X3dAbDesc)]),
     "mspi_mlp_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mspi_mlp_fwd": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mspi_mlp_variant": (C.c_int, [C.POINTER(MlpDesc)]),
     "mspi_postprocess_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mspi_postprocess_u8": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
 }

@@ -418,8 +418,9 @@ static void launch_cfg(const ConvArgs& a, bool v4, int prec, hipStream_t s) {
 using namespace mspi;
 
 namespace mspi {
-int launch_conv_ad(ConvArgs& a, long Ml, int force_bn, int* cfg, hipStream_t s);
-int launch_conv_ad8(ConvArgs& a, long Ml, int bn, int* cfg, hipStream_t s);
+int dma_bn(long Ml, int Cout, int force_bn);
+bool sp_tile_ok(int rows, int bn);
+int launch_conv_dma(ConvArgs& a, long Ml, int rows, int bn, int form, int* cfg, hipStream_t s);
 int launch_conv_sp(ConvArgs& a, long Ml, int bn, int rows, int* cfg, hipStream_t s);
 }
 
@@ -457,9 +458,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 }  // namespace mspi
 
-static int conv_fwd_impl(const MspiConvDesc* d, const float* x, const float* w, const float* bias, const float* res,
-                         const float* gate, float* y, float* ws, int ksplit, mspi_stream_t stream) {
-  MSPI_REQUIRE(d && x && w && y, "mspi_conv_fwd: null argument");
+// Register-staged tiles 0..5: {BM, BN, resident workgroups, relative rate}; 4 and 5 run 8 waves.
+struct Cfg { int bm, bn, slots; float eff; };
+static const Cfg kCfgs[6] = {{128, 128, 512, 1.00f}, {128, 64, 512, 1.06f}, {128, 32, 768, 1.30f}, {64, 64, 1024, 1.25f},
+                             {128, 128, 512, 1.00f}, {256, 128, 256, 1.10f}};
+
+// The kernel instantiation of a conv launch (include/mspi_hip.h, mspi_conv_variant): kind * 10^7 + BM * 10^4 + BN * 10 + form.
+// kind 1 = register-staged, 4 waves (tiles 0..3), 2 = register-staged, 8 waves (tiles 4, 5), 3 = split-K (64 x 64), 4 = LDS-DMA,
+// 128 rows (tiles 6..11), 5 = LDS-DMA, 256 rows (tiles 12..14); form = 2 * scalar gather + prec for kinds 1..3, 0 generic /
+// 1 dense / 2 gate for kinds 4 and 5.  Every check that does not need the weight / output / residual pointers lives here; a
+// descriptor the launch refuses gives -1 with mspi_last_error() set.  conv_fwd_impl switches on this code, so the query cannot
+// drift from what runs.  `tile` receives the register tile (0..5) of kinds 1..3.
+static int conv_select(const MspiConvDesc* d, const float* x, const float* gate, int ksplit, int& tile) {
+  MSPI_REQUIRE(x, "mspi_conv_fwd: null argument");      // aligned16(NULL) holds: a NULL input would pass for a 16-B gather
   MSPI_REQUIRE(d->N > 0 && d->T > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->Cout > 0, "mspi_conv_fwd: empty extent");
   MSPI_REQUIRE(d->kT > 0 && d->kH > 0 && d->kW > 0 && d->strT > 0 && d->strH > 0 && d->strW > 0 && d->padT >= 0 &&
                    d->padH >= 0 && d->padW >= 0,
@@ -472,18 +483,98 @@ static int conv_fwd_impl(const MspiConvDesc* d, const float* x, const float* w, 
                Ho, Wo);
   const long K = (long)d->kT * d->kH * d->kW * d->C;
   MSPI_REQUIRE(d->prec == PREC_F32 || d->prec == PREC_F16X3, "mspi_conv_fwd: unknown precision mode %d", d->prec);
-  MSPI_REQUIRE(d->ldw >= K && (d->ldw & 3) == 0 && aligned16(w), "mspi_conv_fwd: weight rows must be 16-B aligned, ldw >= K");
+  MSPI_REQUIRE(d->ldw >= K && (d->ldw & 3) == 0, "mspi_conv_fwd: weight rows must be 16-B aligned, ldw >= K");
   MSPI_REQUIRE(d->prec == PREC_F32 || ((d->ldw % BK) == 0 && d->w_scale > 0.f),
                "mspi_conv_fwd: f16x3 weights need ldw %% 32 == 0 and a positive w_scale");
   MSPI_REQUIRE(d->ldy >= d->Cout, "mspi_conv_fwd: ldy < Cout");
-  MSPI_REQUIRE(!res || d->ldr >= d->Cout, "mspi_conv_fwd: ldr < Cout");
   const long Ml = (long)d->N * To * Ho * Wo;
   MSPI_REQUIRE(Ml < (1L << 31) && K < (1L << 31), "mspi_conv_fwd: problem too large for 32-bit row index");
 
   const bool v4 = d->sC == 1 && (d->C & 3) == 0 && aligned16(x) && (d->sN & 3) == 0 && (d->sT & 3) == 0 &&
                   (d->sH & 3) == 0 && (d->sW & 3) == 0 && (!gate || aligned16(gate));
-  MSPI_REQUIRE(!gate || (v4 && d->kT == 1 && d->kH == 1 && d->kW == 1),
-               "mspi_conv_fwd: gate needs a 1x1x1 conv on a 16-B aligned channels-last input");
+  const bool dense = d->kT == 1 && d->kH == 1 && d->kW == 1 && d->strT == 1 && d->strH == 1 && d->strW == 1 && d->padT == 0 &&
+                     d->padH == 0 && d->padW == 0;
+  // the gated LDS-DMA form stages its rows without a spatial bounds check: 1x1x1, stride 1, no padding is the contract
+  MSPI_REQUIRE(!gate || (v4 && dense),
+               "mspi_conv_fwd: gate needs a 1x1x1 stride-1 unpadded conv on a 16-B aligned channels-last input");
+  const int form = 2 * (v4 ? 0 : 1) + d->prec;
+  if (ksplit > 1) {
+    // split-K (mspi_conv_splitk_fwd): 64x64 tiles, gridDim.y = ksplit slices of the K loop, then the ordered reduction
+    MSPI_REQUIRE(!gate && (d->Cout & 3) == 0 && (d->ldy & 3) == 0,
+                 "mspi_conv_splitk_fwd: no gate; Cout / ldy / ldr multiples of 4; 16-B aligned pointers");
+    MSPI_REQUIRE(ksplit <= 64 && ksplit <= (d->ldw + BK - 1) / BK, "mspi_conv_splitk_fwd: ksplit = %d", ksplit);
+    MSPI_REQUIRE(((Ml + 63) / 64) * ((d->Cout + 63) / 64) < (1L << 31), "mspi_conv_splitk_fwd: grid too large");
+    tile = 3;
+    return 30000000 + 64 * 10000 + 64 * 10 + form;
+  }
+
+  // LDS-DMA form (conv_gemm_ad.hip): measured faster than the register-staged kernel on deep implicit GEMMs
+  // (multi-tap convs, K >= 2048: 208 vs 199 TFLOP/s on the 3x3x3 readout conv), slower on the 1x1x1 layers
+  // (its per-stage address block costs more than it saves there) -- tools/gemm_probe.py.
+  static const int dma_mode = getenv("MSPI_CONV_DMA") ? atoi(getenv("MSPI_CONV_DMA")) : 1;   // 0 never, 1 auto, 2 always
+  const bool deep_conv = (long)d->kT * d->kH * d->kW > 1 && K >= 2048 && Ml >= 16384;
+  const bool dma_ok = d->prec == PREC_F16X3 && v4;
+  MSPI_REQUIRE(d->tile >= -1 && d->tile <= 14 && (d->tile < 6 || dma_ok) && (d->tile != 8 || d->Cout <= 256),
+               "mspi_conv_fwd: tile %d not available for this call", d->tile);
+  const int dform = gate ? 2 : dense ? 1 : 0;
+  if (d->tile >= 12) {   // LDS-DMA kernel with a 256-row tile and 8 waves sharing one weight tile
+    static const int bn8[3] = {256, 192, 128};
+    const int bn = bn8[d->tile - 12];
+    MSPI_REQUIRE(((Ml + 255) / 256) * ((d->Cout + bn - 1) / bn) < (1L << 31), "mspi_conv_fwd: tile %d could not be launched", d->tile);
+    return 50000000 + 256 * 10000 + bn * 10 + dform;
+  }
+  if (dma_ok && (d->tile >= 6 || (d->tile < 0 && (dma_mode == 2 || (dma_mode == 1 && deep_conv))))) {
+    static const int dma_bn_of[6] = {128, 64, 1, 96, 192, 32};   // tile 6..11 (1 = all columns in one tile)
+    const int bn = dma_bn(Ml, d->Cout, d->tile >= 6 ? dma_bn_of[d->tile - 6] : 0);
+    if (bn > 0 && ((Ml + 127) / 128) * ((d->Cout + bn - 1) / bn) < (1L << 31)) return 40000000 + 128 * 10000 + bn * 10 + dform;
+    // heuristic: no LDS-DMA tile for this request, the register-staged kernel takes it
+    MSPI_REQUIRE(d->tile < 0, "mspi_conv_fwd: tile %d could not be launched", d->tile);
+  }
+
+  // Tile choice.  time ~ rounds x (work of one workgroup): rounds = ceil(blocks / resident slots) -- whole rounds,
+  // because a 588-block grid on 512 slots takes as long as 1024 blocks would (measured: tools/gemm_probe.py) --
+  // and per-workgroup work ~ bm*bn*(K + K0) with K0 standing for the prologue + epilogue.  All tiles sustain about
+  // the same rate on big grids (eff), so the choice is mostly about padding waste and round quantisation.
+  static const int force = getenv("MSPI_CONV_TILE") ? atoi(getenv("MSPI_CONV_TILE")) : -1;
+  int best = 3;
+  double best_cost = 1e300;
+  for (int i = 0; i < 4; ++i) {
+    const long tm = (Ml + kCfgs[i].bm - 1) / kCfgs[i].bm, tn = (d->Cout + kCfgs[i].bn - 1) / kCfgs[i].bn;
+    const long blocks = tm * tn;
+    double rounds = (double)blocks / kCfgs[i].slots;
+    if (rounds < 6.0) rounds = (double)((blocks + kCfgs[i].slots - 1) / kCfgs[i].slots);
+    const double cost = rounds * kCfgs[i].bm * kCfgs[i].bn * kCfgs[i].eff * ((double)K + 192.0);
+    if (cost < best_cost) { best_cost = cost; best = i; }
+  }
+  if (best == 0 && !getenv("MSPI_CONV_4WAVE")) best = 4;   // 128x128 runs best with 8 waves (32x64 per wave, 4 waves/SIMD)
+  if (force >= 0 && force < 6) best = force;
+  if (d->tile >= 0) best = d->tile;
+  const long nb = ((Ml + kCfgs[best].bm - 1) / kCfgs[best].bm) * ((d->Cout + kCfgs[best].bn - 1) / kCfgs[best].bn);
+  MSPI_REQUIRE(nb < (1L << 31), "mspi_conv_fwd: grid too large");
+  tile = best;
+  return (best >= 4 ? 20000000 : 10000000) + kCfgs[best].bm * 10000 + kCfgs[best].bn * 10 + form;
+}
+
+extern "C" int mspi_conv_variant(const MspiConvDesc* d, const float* x, const float* gate, int32_t ksplit) {
+  MSPI_REQUIRE(d, "mspi_conv_variant: null descriptor");
+  int tile = 0;
+  return conv_select(d, x, gate, ksplit, tile);
+}
+
+static int conv_fwd_impl(const MspiConvDesc* d, const float* x, const float* w, const float* bias, const float* res,
+                         const float* gate, float* y, float* ws, int ksplit, mspi_stream_t stream) {
+  MSPI_REQUIRE(d && x && w && y, "mspi_conv_fwd: null argument");
+  MSPI_REQUIRE(!ws || ksplit >= 2, "mspi_conv_splitk_fwd: ksplit = %d", ksplit);
+  int tile = 0;
+  const int variant = conv_select(d, x, gate, ws ? ksplit : 1, tile);
+  if (variant < 0) return variant;
+  const int kind = variant / 10000000, form = variant % 10;
+  const bool v4 = kind <= 3 ? (form & 2) == 0 : true;
+  MSPI_REQUIRE(aligned16(w), "mspi_conv_fwd: weight rows must be 16-B aligned, ldw >= K");
+  MSPI_REQUIRE(!res || d->ldr >= d->Cout, "mspi_conv_fwd: ldr < Cout");
+  const int To = d->To, Ho = d->Ho, Wo = d->Wo;
+  const long K = (long)d->kT * d->kH * d->kW * d->C;
+  const long Ml = (long)d->N * To * Ho * Wo;
 
   ConvArgs a;
   a.x = x; a.w = w; a.bias = bias; a.res = res; a.gate = gate; a.y = y;
@@ -504,17 +595,12 @@ static int conv_fwd_impl(const MspiConvDesc* d, const float* x, const float* w, 
                   d->padW == 0 && d->sC == 1 && d->sH == (int64_t)d->W * d->sW && d->sT == (int64_t)d->H * d->sH &&
                   d->sN == (int64_t)d->T * d->sT) ? 1 : 0;
   a.wb = (d->prec == PREC_F16X3) ? (const _Float16*)d->w_blocked : nullptr; a.xs = nullptr; a.ldxs = 0; a.xplane = 0; a.ys = nullptr; a.ldys = 0; a.yplane = 0;
-  if (ws) {
-    // split-K (mspi_conv_splitk_fwd): 64x64 tiles, gridDim.y = ksplit slices of the K loop, then the ordered reduction
-    MSPI_REQUIRE(!gate && (d->Cout & 3) == 0 && (d->ldy & 3) == 0 && (!res || (d->ldr & 3) == 0) && aligned16(y) && aligned16(ws) &&
-                     (!res || aligned16(res)) && (!bias || aligned16(bias)),
+  hipStream_t s = (hipStream_t)stream;
+  if (kind == 3) {
+    MSPI_REQUIRE((!res || (d->ldr & 3) == 0) && aligned16(y) && aligned16(ws) && (!res || aligned16(res)) && (!bias || aligned16(bias)),
                  "mspi_conv_splitk_fwd: no gate; Cout / ldy / ldr multiples of 4; 16-B aligned pointers");
-    MSPI_REQUIRE(ksplit >= 2 && ksplit <= 64 && ksplit <= (d->ldw + BK - 1) / BK, "mspi_conv_splitk_fwd: ksplit = %d", ksplit);
     a.tiles_n = (d->Cout + 63) / 64;
-    const long nb = ((Ml + 63) / 64) * a.tiles_n;
-    MSPI_REQUIRE(nb < (1L << 31), "mspi_conv_splitk_fwd: grid too large");
-    a.nblocks = (int)nb;
-    hipStream_t s = (hipStream_t)stream;
+    a.nblocks = (int)(((Ml + 63) / 64) * a.tiles_n);
     g_last_cfg = (64 << 16) | (64 << 4) | (d->prec << 1) | (v4 ? 0 : 1);
     launch_cfg<64, 64, 2, 2>(a, v4, d->prec, s);
     const long total = Ml * (d->Cout >> 2);
@@ -523,62 +609,18 @@ static int conv_fwd_impl(const MspiConvDesc* d, const float* x, const float* w, 
                        Ml, d->Cout, bias, res, (long)d->ldr, y, (long)d->ldy, d->act, mspi::g_status_word);
     return check_launch("mspi_conv_splitk_fwd");
   }
-
-  // LDS-DMA form (conv_gemm_ad.hip): measured faster than the register-staged kernel on deep implicit GEMMs
-  // (multi-tap convs, K >= 2048: 208 vs 199 TFLOP/s on the 3x3x3 readout conv), slower on the 1x1x1 layers
-  // (its per-stage address block costs more than it saves there) -- tools/gemm_probe.py.
-  static const int dma_mode = getenv("MSPI_CONV_DMA") ? atoi(getenv("MSPI_CONV_DMA")) : 1;   // 0 never, 1 auto, 2 always
-  const bool deep_conv = (long)d->kT * d->kH * d->kW > 1 && K >= 2048 && Ml >= 16384;
-  const bool dma_ok = d->prec == PREC_F16X3 && v4;
-  MSPI_REQUIRE(d->tile >= -1 && d->tile <= 14 && (d->tile < 6 || dma_ok) && (d->tile != 8 || d->Cout <= 256),
-               "mspi_conv_fwd: tile %d not available for this call", d->tile);
-  if (d->tile >= 12) {   // LDS-DMA kernel with a 256-row tile and 8 waves sharing one weight tile
-    static const int bn8[3] = {256, 192, 128};
+  if (kind >= 4) {
     int cfg = 0;
-    const int rc = launch_conv_ad8(a, Ml, bn8[d->tile - 12], &cfg, (hipStream_t)stream);
-    MSPI_REQUIRE(rc == 0, "mspi_conv_fwd: tile %d could not be launched", d->tile);
+    const int rc = launch_conv_dma(a, Ml, kind == 5 ? 256 : 128, (variant / 10) % 1000, form, &cfg, s);
+    MSPI_REQUIRE(rc == 0, "mspi_conv_fwd: variant %d could not be launched", variant);
     g_last_cfg = cfg;
     return check_launch("mspi_conv_fwd");
   }
-  if (dma_ok && (d->tile >= 6 || (d->tile < 0 && (dma_mode == 2 || (dma_mode == 1 && deep_conv))))) {
-    static const int dma_bn[6] = {128, 64, 1, 96, 192, 32};   // tile 6..11 (1 = all columns in one tile)
-    int cfg = 0;
-    const int rc = launch_conv_ad(a, Ml, d->tile >= 6 ? dma_bn[d->tile - 6] : 0, &cfg, (hipStream_t)stream);
-    if (rc >= 0) {
-      g_last_cfg = cfg;
-      return rc == 0 ? check_launch("mspi_conv_fwd") : rc;
-    }
-  }
-
-  // Tile choice.  time ~ rounds x (work of one workgroup): rounds = ceil(blocks / resident slots) -- whole rounds,
-  // because a 588-block grid on 512 slots takes as long as 1024 blocks would (measured: tools/gemm_probe.py) --
-  // and per-workgroup work ~ bm*bn*(K + K0) with K0 standing for the prologue + epilogue.  All tiles sustain about
-  // the same rate on big grids (eff), so the choice is mostly about padding waste and round quantisation.
-  struct Cfg { int bm, bn, slots; float eff; };
-  static const Cfg cfgs[6] = {{128, 128, 512, 1.00f}, {128, 64, 512, 1.06f}, {128, 32, 768, 1.30f}, {64, 64, 1024, 1.25f},
-                              {128, 128, 512, 1.00f}, {256, 128, 256, 1.10f}};
-  static const int force = getenv("MSPI_CONV_TILE") ? atoi(getenv("MSPI_CONV_TILE")) : -1;
-  int best = 3;
-  double best_cost = 1e300;
-  for (int i = 0; i < 4; ++i) {
-    const long tm = (Ml + cfgs[i].bm - 1) / cfgs[i].bm, tn = (d->Cout + cfgs[i].bn - 1) / cfgs[i].bn;
-    const long blocks = tm * tn;
-    double rounds = (double)blocks / cfgs[i].slots;
-    if (rounds < 6.0) rounds = (double)((blocks + cfgs[i].slots - 1) / cfgs[i].slots);
-    const double cost = rounds * cfgs[i].bm * cfgs[i].bn * cfgs[i].eff * ((double)K + 192.0);
-    if (cost < best_cost) { best_cost = cost; best = i; }
-  }
-  if (best == 0 && !getenv("MSPI_CONV_4WAVE")) best = 4;   // 128x128 runs best with 8 waves (32x64 per wave, 4 waves/SIMD)
-  if (force >= 0 && force < 6) best = force;
-  if (d->tile >= 0) best = d->tile;
-  const int BMs = cfgs[best].bm, BNs = cfgs[best].bn;
+  const int BMs = kCfgs[tile].bm, BNs = kCfgs[tile].bn;
   a.tiles_n = (d->Cout + BNs - 1) / BNs;
-  const long nb = ((Ml + BMs - 1) / BMs) * a.tiles_n;
-  MSPI_REQUIRE(nb < (1L << 31), "mspi_conv_fwd: grid too large");
-  a.nblocks = (int)nb;
-  hipStream_t s = (hipStream_t)stream;
-  g_last_cfg = (BMs << 16) | (BNs << 4) | (best >= 4 ? 8 : 0) | (d->prec << 1) | (v4 ? 0 : 1);
-  switch (best) {
+  a.nblocks = (int)(((Ml + BMs - 1) / BMs) * a.tiles_n);
+  g_last_cfg = (BMs << 16) | (BNs << 4) | (tile >= 4 ? 8 : 0) | (d->prec << 1) | (v4 ? 0 : 1);
+  switch (tile) {
     case 0: launch_cfg<128, 128, 2, 2>(a, v4, d->prec, s); break;
     case 1: launch_cfg<128, 64, 2, 2>(a, v4, d->prec, s); break;
     case 2: launch_cfg<128, 32, 4, 1>(a, v4, d->prec, s); break;
@@ -666,19 +708,51 @@ extern "C" int mspi_join_planes_fwd(const void* planes, int64_t ldi, int64_t pla
   return check_launch("mspi_join_planes_fwd");
 }
 
-extern "C" int mspi_gemm_sp_fwd(const MspiConvDesc* d, const void* x_planes, int64_t ldx, int64_t xplane, const float* w,
-                                const float* bias, const float* res, float* y, void* y_planes, int64_t ldys, int64_t yplane,
-                                mspi_stream_t stream) {
-  MSPI_REQUIRE(d && x_planes && w && (y || y_planes), "mspi_gemm_sp_fwd: null argument");
+// The instantiation mspi_gemm_sp_fwd runs (include/mspi_hip.h, mspi_gemm_sp_variant): kind * 10^7 + BM * 10^4 + BN * 10 + form,
+// kind 6 = 128 rows / 4 waves, 7 = 256 rows / 8 waves (conv_gemm_dma_kernel<BN, false, true, NW, true>), form 0 = fp32 rows
+// out, 1 = blocked planes out; -1 = a descriptor the launch refuses.  mspi_gemm_sp_fwd switches on this code.
+static int gemm_sp_select(const MspiConvDesc* d, bool planes_out) {
   MSPI_REQUIRE(d->kT == 1 && d->kH == 1 && d->kW == 1 && d->strT == 1 && d->strH == 1 && d->strW == 1 && d->padT == 0 &&
                    d->padH == 0 && d->padW == 0, "mspi_gemm_sp_fwd: a plain GEMM on rows (1x1x1, stride 1, no padding)");
   MSPI_REQUIRE(d->prec == PREC_F16X3 && d->w_scale > 0.f && d->C > 0 && (d->C % BK) == 0 && d->ldw == d->C,
                "mspi_gemm_sp_fwd: f16x3 weights, K a multiple of 32 with ldw == K");
+  const long Ml = (long)d->N * d->T * d->H * d->W;
+  MSPI_REQUIRE(d->N > 0 && d->T > 0 && d->H > 0 && d->W > 0 && d->Cout > 0 && Ml < (1L << 31), "mspi_gemm_sp_fwd: bad extent");
+  MSPI_REQUIRE(!planes_out || (d->Cout % 32) == 0, "mspi_gemm_sp_fwd: blocked output planes need Cout %% 32 == 0");
+  MSPI_REQUIRE(planes_out || d->ldy >= d->Cout, "mspi_gemm_sp_fwd: ldy < Cout");
+  int bn, rows = 128;
+  switch (d->tile) {
+    case 6: bn = 128; break;
+    case 7: bn = 64; break;
+    case 9: bn = 96; break;
+    case 10: bn = 192; break;
+    case 11: bn = 256; break;
+    case 12: bn = 256; rows = 256; break;
+    case 13: bn = 192; rows = 256; break;
+    case 14: bn = 128; rows = 256; break;
+    default: bn = d->Cout <= 64 ? 64 : (d->Cout % 192 == 0 ? 192 : 128); break;
+  }
+  MSPI_REQUIRE(sp_tile_ok(rows, bn) && ((Ml + rows - 1) / rows) * ((d->Cout + bn - 1) / bn) < (1L << 31),
+               "mspi_gemm_sp_fwd: tile %d could not be launched", d->tile);
+  return (rows == 256 ? 70000000 : 60000000) + rows * 10000 + bn * 10 + (planes_out ? 1 : 0);
+}
+
+extern "C" int mspi_gemm_sp_variant(const MspiConvDesc* d, const void* y_planes) {
+  MSPI_REQUIRE(d, "mspi_gemm_sp_variant: null descriptor");
+  return gemm_sp_select(d, y_planes != nullptr);
+}
+
+extern "C" int mspi_gemm_sp_fwd(const MspiConvDesc* d, const void* x_planes, int64_t ldx, int64_t xplane, const float* w,
+                                const float* bias, const float* res, float* y, void* y_planes, int64_t ldys, int64_t yplane,
+                                mspi_stream_t stream) {
+  MSPI_REQUIRE(d && x_planes && w && (y || y_planes), "mspi_gemm_sp_fwd: null argument");
+  const int variant = gemm_sp_select(d, y_planes != nullptr);
+  if (variant < 0) return variant;
   MSPI_REQUIRE(ldx == d->C && (xplane & 7) == 0 && aligned16(x_planes) && aligned16(w),
                "mspi_gemm_sp_fwd: blocked input planes have ldx == K");
   const long Ml = (long)d->N * d->T * d->H * d->W;
   const long Mp = (Ml + 15) / 16 * 16;
-  MSPI_REQUIRE(Ml > 0 && Ml < (1L << 31) && xplane >= Mp * ldx, "mspi_gemm_sp_fwd: bad extent (plane >= roundup16(M) * K)");
+  MSPI_REQUIRE(xplane >= Mp * ldx, "mspi_gemm_sp_fwd: bad extent (plane >= roundup16(M) * K)");
   MSPI_REQUIRE(!y_planes || (ldys == d->Cout && yplane >= Mp * ldys && (d->Cout % 32) == 0 && (yplane & 7) == 0 &&
                               aligned16(y_planes)), "mspi_gemm_sp_fwd: blocked output planes need Cout %% 32 == 0, ldys == Cout, plane >= roundup16(M) * Cout");
   MSPI_REQUIRE(!y || d->ldy >= d->Cout, "mspi_gemm_sp_fwd: ldy < Cout");
@@ -698,18 +772,7 @@ extern "C" int mspi_gemm_sp_fwd(const MspiConvDesc* d, const void* x_planes, int
   a.wb = nullptr;      // (the pre-split form takes blocked weights through `w`)
   a.xs = (const _Float16*)x_planes; a.ldxs = ldx; a.xplane = xplane;
   a.ys = (_Float16*)y_planes; a.ldys = ldys; a.yplane = yplane;
-  int bn, rows = 128;
-  switch (d->tile) {
-    case 6: bn = 128; break;
-    case 7: bn = 64; break;
-    case 9: bn = 96; break;
-    case 10: bn = 192; break;
-    case 11: bn = 256; break;
-    case 12: bn = 256; rows = 256; break;
-    case 13: bn = 192; rows = 256; break;
-    case 14: bn = 128; rows = 256; break;
-    default: bn = d->Cout <= 64 ? 64 : (d->Cout % 192 == 0 ? 192 : 128); break;
-  }
+  const int rows = (variant / 10000) % 1000, bn = (variant / 10) % 1000;
   int cfg = 0;
   const int rc = launch_conv_sp(a, Ml, bn, rows, &cfg, (hipStream_t)stream);
   MSPI_REQUIRE(rc == 0, "mspi_gemm_sp_fwd: tile %d could not be launched", d->tile);

@@ -200,9 +200,10 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_gemm_dma_kernel(const ConvArg
     }
     if (GATE) {
       const int kk = k0 + 16 * lh + 8 * sub;
-      const bool ok = kk < p.C;
-      f.g0 = *reinterpret_cast<const float4*>(gate_row + (ok ? kk : 0));
-      f.g1 = *reinterpret_cast<const float4*>(gate_row + (ok ? kk + 4 : 0));
+      // each half checked on its own: with C % 8 == 4 the second float4 of the last chunk lies past the sample's gate row
+      // (the last sample's: past the buffer).  Its activations are zero; a clamped read keeps swish(0 * g) = 0 finite.
+      f.g0 = *reinterpret_cast<const float4*>(gate_row + (kk < p.C ? kk : 0));
+      f.g1 = *reinterpret_cast<const float4*>(gate_row + (kk + 4 < p.C ? kk + 4 : 0));
     }
   };
   auto frag_split = [&](Frag& f) {
@@ -386,15 +387,12 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_gemm_dma_kernel(const ConvArg
   report_nonfinite(p.status, bad);
 }
 
-// returns 0 when launched, -100 when this path does not apply (caller falls back to conv_gemm.hip).
-// force_bn: 0 = heuristic; else the column tile (a multiple of 32 up to 256; 1 = "all columns in one tile").
+// form (mspi_conv_variant): 0 = generic gather, 1 = DENSE (1x1x1, stride 1, no padding), 2 = DENSE with the squeeze-excite gate
 template <int BN, int NW = 4>
-static void launch_bn(const ConvArgs& a, hipStream_t s) {
+static void launch_bn(const ConvArgs& a, int form, hipStream_t s) {
   const dim3 g(a.nblocks), b(64 * NW);
-  const bool dense = a.kT * a.kH * a.kW == 1 && a.strT == 1 && a.strH == 1 && a.strW == 1 && a.padT == 0 && a.padH == 0 &&
-                     a.padW == 0;
-  if (a.gate) hipLaunchKernelGGL((conv_gemm_dma_kernel<BN, true, true, NW>), g, b, 0, s, a);   // the gate implies 1x1x1
-  else if (dense) hipLaunchKernelGGL((conv_gemm_dma_kernel<BN, false, true, NW>), g, b, 0, s, a);
+  if (form == 2) hipLaunchKernelGGL((conv_gemm_dma_kernel<BN, true, true, NW>), g, b, 0, s, a);
+  else if (form == 1) hipLaunchKernelGGL((conv_gemm_dma_kernel<BN, false, true, NW>), g, b, 0, s, a);
   else hipLaunchKernelGGL((conv_gemm_dma_kernel<BN, false, false, NW>), g, b, 0, s, a);
 }
 
@@ -404,7 +402,14 @@ static void launch_sp(const ConvArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((conv_gemm_dma_kernel<BN, false, true, NW, true>), dim3(a.nblocks), dim3(64 * NW), 0, s, a);
 }
 
+// the instantiations mspi_gemm_sp_fwd has: 128 rows x {64, 96, 128, 192, 256}, 256 rows x {128, 192, 256}
+bool sp_tile_ok(int rows, int bn) {
+  return rows == 256 ? (bn == 128 || bn == 192 || bn == 256) : rows == 128 && (bn == 64 || bn == 96 || bn == 128 || bn == 192 || bn == 256);
+}
+
+// returns 0 when launched, -100 when no instantiation matches (the selection in conv_gemm.hip rules that out)
 int launch_conv_sp(ConvArgs& a, long Ml, int bn, int rows, int* cfg, hipStream_t s) {
+  if (!sp_tile_ok(rows, bn)) return -100;
   a.tiles_n = (int)((a.Cout + bn - 1) / bn);
   const long nb = ((Ml + rows - 1) / rows) * a.tiles_n;
   if (nb >= (1L << 31)) return -100;
@@ -414,8 +419,7 @@ int launch_conv_sp(ConvArgs& a, long Ml, int bn, int rows, int* cfg, hipStream_t
     switch (bn) {
       case 128: launch_sp<128, 8>(a, s); break;
       case 192: launch_sp<192, 8>(a, s); break;
-      case 256: launch_sp<256, 8>(a, s); break;
-      default: return -100;
+      default: launch_sp<256, 8>(a, s); break;
     }
     return 0;
   }
@@ -424,52 +428,52 @@ int launch_conv_sp(ConvArgs& a, long Ml, int bn, int rows, int* cfg, hipStream_t
     case 96: launch_sp<96, 4>(a, s); break;
     case 128: launch_sp<128, 4>(a, s); break;
     case 192: launch_sp<192, 4>(a, s); break;
-    case 256: launch_sp<256, 4>(a, s); break;
-    default: return -100;
+    default: launch_sp<256, 4>(a, s); break;
   }
   return 0;
 }
 
-// 256 x BN tile, 8 waves (tile codes 12..14)
-int launch_conv_ad8(ConvArgs& a, long Ml, int bn, int* cfg, hipStream_t s) {
-  a.tiles_n = (int)((a.Cout + bn - 1) / bn);
-  const long nb = ((Ml + 255) / 256) * a.tiles_n;
-  if (nb >= (1L << 31)) return -100;
-  a.nblocks = (int)nb;
-  *cfg = (256 << 16) | (bn << 4) | 8 | (PREC_F16X3 << 1) | 4;
-  switch (bn) {
-    case 128: launch_bn<128, 8>(a, s); break;
-    case 192: launch_bn<192, 8>(a, s); break;
-    case 256: launch_bn<256, 8>(a, s); break;
-    default: return -100;
-  }
-  return 0;
-}
-
-int launch_conv_ad(ConvArgs& a, long Ml, int force_bn_arg, int* cfg, hipStream_t s) {
+// Column tile of the 128-row LDS-DMA kernel.  force_bn: 0 = heuristic (or MSPI_CONV_BN), else the column tile (a multiple of
+// 32 up to 256; 1 = "all columns in one tile").  Returns 0 when no instantiation covers the request.
+int dma_bn(long Ml, int Cout, int force_bn_arg) {
   const long tm = (Ml + 127) / 128;
-  const long t128 = (a.Cout + 127) / 128, t64 = (a.Cout + 63) / 64;
+  const long t128 = (Cout + 127) / 128, t64 = (Cout + 63) / 64;
   static const int env_bn = getenv("MSPI_CONV_BN") ? atoi(getenv("MSPI_CONV_BN")) : 0;
   int bn = force_bn_arg ? force_bn_arg : env_bn;
-  if (bn == 1) {   // one column tile holding every output channel: the activations are fetched exactly once
-    bn = (a.Cout + 31) / 32 * 32;
-    if (bn > 256) return -100;
-  }
+  if (bn == 1) bn = (Cout + 31) / 32 * 32;   // one column tile holding every output channel: the activations are fetched exactly once
   if (bn == 0) bn = (t64 * 64 < t128 * 128 || tm * t128 < 384) ? 64 : 128;   // less padding, or a grid that fills the chip
+  switch (bn) {
+    case 32: case 64: case 96: case 128: case 160: case 192: case 224: case 256: return bn;
+    default: return 0;
+  }
+}
+
+// LDS-DMA launch of the instantiation the selection picked: rows 128 (4 waves, BN 32..256) or 256 (8 waves, BN 128 / 192 /
+// 256), form as at launch_bn.  Returns 0 when launched, -100 when no instantiation matches.
+int launch_conv_dma(ConvArgs& a, long Ml, int rows, int bn, int form, int* cfg, hipStream_t s) {
   a.tiles_n = (int)((a.Cout + bn - 1) / bn);
-  const long nb = tm * a.tiles_n;
+  const long nb = ((Ml + rows - 1) / rows) * a.tiles_n;
   if (nb >= (1L << 31)) return -100;
   a.nblocks = (int)nb;
-  *cfg = (128 << 16) | (bn << 4) | (PREC_F16X3 << 1) | 4;   // loader code 4 = LDS-DMA
+  *cfg = (rows << 16) | (bn << 4) | (rows == 256 ? 8 : 0) | (PREC_F16X3 << 1) | 4;   // loader code 4 = LDS-DMA
+  if (rows == 256) {
+    switch (bn) {
+      case 128: launch_bn<128, 8>(a, form, s); break;
+      case 192: launch_bn<192, 8>(a, form, s); break;
+      case 256: launch_bn<256, 8>(a, form, s); break;
+      default: return -100;
+    }
+    return 0;
+  }
   switch (bn) {
-    case 32: launch_bn<32>(a, s); break;
-    case 64: launch_bn<64>(a, s); break;
-    case 96: launch_bn<96>(a, s); break;
-    case 128: launch_bn<128>(a, s); break;
-    case 160: launch_bn<160>(a, s); break;
-    case 192: launch_bn<192>(a, s); break;
-    case 224: launch_bn<224>(a, s); break;
-    case 256: launch_bn<256>(a, s); break;
+    case 32: launch_bn<32>(a, form, s); break;
+    case 64: launch_bn<64>(a, form, s); break;
+    case 96: launch_bn<96>(a, form, s); break;
+    case 128: launch_bn<128>(a, form, s); break;
+    case 160: launch_bn<160>(a, form, s); break;
+    case 192: launch_bn<192>(a, form, s); break;
+    case 224: launch_bn<224>(a, form, s); break;
+    case 256: launch_bn<256>(a, form, s); break;
     default: return -100;
   }
   return 0;

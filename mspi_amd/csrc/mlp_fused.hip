@@ -365,17 +365,36 @@ extern "C" size_t mspi_mlp_packed_bytes(int C, int hidden) {
   return (size_t)(hidden / 32) * ((size_t)(C / 16) * 2048 + 2 * (size_t)(C / 32) * 2048);
 }
 
-extern "C" int mspi_mlp_fwd(const MspiMlpDesc* d, const void* x, const void* gamma, const void* beta, const void* w_packed,
-                            const void* b1, const void* b2, const void* res, void* y, void* stream) {
-  MSPI_REQUIRE(d && x && w_packed && b1 && b2 && y, "mspi_mlp_fwd: null argument");
+// The instantiation mspi_mlp_fwd runs (include/mspi_hip.h, mspi_mlp_variant): mlp_fused_kernel<C, TM, NS, NWV> as
+// C * 1000 + TM * 100 + NS * 10 + NWV; -1 = a descriptor the launch refuses.  mspi_mlp_fwd switches on this code.
+static int mlp_select(const MspiMlpDesc* d, bool ln_params) {
   MSPI_REQUIRE(d->C == 96 || d->C == 192, "mspi_mlp_fwd: C = %d not supported (96, 192)", d->C);
   MSPI_REQUIRE(d->hidden % 32 == 0 && d->hidden >= 32 && d->hidden <= 1024, "mspi_mlp_fwd: hidden = %d", d->hidden);
   MSPI_REQUIRE(d->M >= 1 && d->M < (1L << 31), "mspi_mlp_fwd: M = %ld", (long)d->M);
-  MSPI_REQUIRE(d->ldx >= d->C && d->ldy >= d->C && d->ldx % 4 == 0 && d->ldy % 4 == 0 && (!res || (d->ldr >= d->C && d->ldr % 4 == 0)),
+  MSPI_REQUIRE(d->ldx >= d->C && d->ldy >= d->C && d->ldx % 4 == 0 && d->ldy % 4 == 0,
                "mspi_mlp_fwd: row strides must be >= C and multiples of 4 floats");
   MSPI_REQUIRE(d->act == MSPI_ACT_GELU, "mspi_mlp_fwd: only MSPI_ACT_GELU between the layers (act = %d)", d->act);
-  MSPI_REQUIRE(!d->ln || (gamma && beta), "mspi_mlp_fwd: LayerNorm needs gamma and beta");
+  MSPI_REQUIRE(!d->ln || ln_params, "mspi_mlp_fwd: LayerNorm needs gamma and beta");
   MSPI_REQUIRE(d->w1_scale > 0.f && d->w2_scale > 0.f, "mspi_mlp_fwd: weight scales must be positive");
+  MSPI_REQUIRE(d->C != 96 || d->hidden <= 512, "mspi_mlp_fwd: hidden = %d > 512 with C = 96", d->hidden);
+  static const int variant = getenv("MSPI_MLP_TM") ? atoi(getenv("MSPI_MLP_TM")) : 0;
+  if (d->C == 96) return variant == 2 ? 96244 : 96134;
+  // C = 192: 8 waves (256 rows) per workgroup where that still gives every CU a workgroup (measured at M = 100352: 315.9 ->
+  // 277.6 us); MSPI_MLP_TM=4 / 8 force one form for an A/B
+  return (variant == 8 || (variant != 4 && d->M >= 256L * 256)) ? 192138 : 192134;
+}
+
+extern "C" int mspi_mlp_variant(const MspiMlpDesc* d) {
+  MSPI_REQUIRE(d, "mspi_mlp_variant: null descriptor");
+  return mlp_select(d, true);
+}
+
+extern "C" int mspi_mlp_fwd(const MspiMlpDesc* d, const void* x, const void* gamma, const void* beta, const void* w_packed,
+                            const void* b1, const void* b2, const void* res, void* y, void* stream) {
+  MSPI_REQUIRE(d && x && w_packed && b1 && b2 && y, "mspi_mlp_fwd: null argument");
+  const int variant = mlp_select(d, gamma && beta);
+  if (variant < 0) return variant;
+  MSPI_REQUIRE(!res || (d->ldr >= d->C && d->ldr % 4 == 0), "mspi_mlp_fwd: row strides must be >= C and multiples of 4 floats");
   MlpArgs a;
   a.x = (const float*)x; a.gamma = (const float*)gamma; a.beta = (const float*)beta; a.wp = (const unsigned char*)w_packed;
   a.b1 = (const float*)b1; a.b2 = (const float*)b2; a.res = (const float*)res; a.y = (float*)y;
@@ -383,16 +402,13 @@ extern "C" int mspi_mlp_fwd(const MspiMlpDesc* d, const void* x, const void* gam
   a.nch = d->hidden / 32; a.ln = d->ln; a.act = d->act; a.eps = d->eps;
   a.inv_s1 = 1.0f / d->w1_scale; a.inv_s2 = 1.0f / d->w2_scale;
   a.status = g_status_word;
-  static const int variant = getenv("MSPI_MLP_TM") ? atoi(getenv("MSPI_MLP_TM")) : 0;
-  int rc;
-  MSPI_REQUIRE(d->C != 96 || d->hidden <= 512, "mspi_mlp_fwd: hidden = %d > 512 with C = 96", d->hidden);
-  if (d->C == 96) rc = (variant == 2) ? launch_mlp<96, 2, 4>(a, (hipStream_t)stream) :
-                       launch_mlp<96, 1, 3>(a, (hipStream_t)stream);
-  // C = 192: 8 waves (256 rows) per workgroup where that still gives every CU a workgroup (measured at M = 100352: 315.9 ->
-  // 277.6 us); MSPI_MLP_TM=4 / 8 force one form for an A/B
-  else if (variant == 8 || (variant != 4 && a.M >= 256L * 256)) rc = launch_mlp<192, 1, 3, 8>(a, (hipStream_t)stream);
-  else rc = launch_mlp<192, 1, 3>(a, (hipStream_t)stream);
-  (void)rc;
+  hipStream_t s = (hipStream_t)stream;
+  switch (variant) {
+    case 96244: launch_mlp<96, 2, 4>(a, s); break;
+    case 96134: launch_mlp<96, 1, 3>(a, s); break;
+    case 192138: launch_mlp<192, 1, 3, 8>(a, s); break;
+    default: launch_mlp<192, 1, 3>(a, s); break;
+  }
   return check_launch("mspi_mlp_fwd");
 }
 
@@ -560,16 +576,30 @@ extern "C" int mspi_rowgemm_supported(int32_t K, int32_t N) {
   return rowgemm_ksb(K) != 0 && N >= 4 && N <= 1024;
 }
 
-extern "C" int mspi_rowgemm_fwd(const MspiRowGemmDesc* d, const void* x, const void* w_packed, const void* bias, const void* res,
-                                const void* gate, void* y, void* stream) {
-  MSPI_REQUIRE(d && x && w_packed && y, "mspi_rowgemm_fwd: null argument");
+// The instantiation mspi_rowgemm_fwd runs (include/mspi_hip.h, mspi_rowgemm_variant): rowgemm_kernel<KSB, GATE> as
+// KSB * 10 + GATE; -1 = a descriptor the launch refuses.  mspi_rowgemm_fwd switches on this code.
+static int rowgemm_select(const MspiRowGemmDesc* d, bool gate) {
   MSPI_REQUIRE(d->M >= 1 && d->M < (1L << 31) && d->K >= 4 && d->N >= 4 && d->K % 4 == 0 && d->N % 4 == 0,
                "mspi_rowgemm_fwd: M = %ld, K = %d, N = %d (K, N: storage columns, multiples of 4)", (long)d->M, d->K, d->N);
   MSPI_REQUIRE(mspi_rowgemm_supported(d->K, d->N), "mspi_rowgemm_fwd: K = %d / N = %d outside the thin-GEMM range", d->K, d->N);
-  MSPI_REQUIRE(d->ldx >= d->K && d->ldy >= d->N && d->ldx % 4 == 0 && d->ldy % 4 == 0 && (!res || (d->ldr >= d->N && d->ldr % 4 == 0)),
+  MSPI_REQUIRE(d->ldx >= d->K && d->ldy >= d->N && d->ldx % 4 == 0 && d->ldy % 4 == 0,
                "mspi_rowgemm_fwd: row strides must cover the row and be multiples of 4 floats");
   MSPI_REQUIRE(!gate || (d->rows_per_sample > 0 && d->ldg >= d->K && d->ldg % 4 == 0), "mspi_rowgemm_fwd: gate needs rows_per_sample and ldg");
   MSPI_REQUIRE(d->w_scale > 0.f, "mspi_rowgemm_fwd: w_scale must be positive");
+  return rowgemm_ksb(d->K) * 10 + (gate ? 1 : 0);
+}
+
+extern "C" int mspi_rowgemm_variant(const MspiRowGemmDesc* d, int32_t has_gate) {
+  MSPI_REQUIRE(d, "mspi_rowgemm_variant: null descriptor");
+  return rowgemm_select(d, has_gate != 0);
+}
+
+extern "C" int mspi_rowgemm_fwd(const MspiRowGemmDesc* d, const void* x, const void* w_packed, const void* bias, const void* res,
+                                const void* gate, void* y, void* stream) {
+  MSPI_REQUIRE(d && x && w_packed && y, "mspi_rowgemm_fwd: null argument");
+  const int variant = rowgemm_select(d, gate != nullptr);
+  if (variant < 0) return variant;
+  MSPI_REQUIRE(!res || (d->ldr >= d->N && d->ldr % 4 == 0), "mspi_rowgemm_fwd: row strides must cover the row and be multiples of 4 floats");
   RowGemmArgs a;
   a.x = (const float*)x; a.wp = (const unsigned char*)w_packed; a.bias = (const float*)bias; a.res = (const float*)res;
   a.gate = (const float*)gate; a.y = (float*)y;
@@ -577,7 +607,7 @@ extern "C" int mspi_rowgemm_fwd(const MspiRowGemmDesc* d, const void* x, const v
   a.K = d->K; a.N = d->N; a.nch = (d->N + 31) / 32; a.act = d->act; a.inv_s = 1.0f / d->w_scale;
   a.rows_per_sample = d->rows_per_sample;
   a.status = g_status_word;
-  const int ksb = rowgemm_ksb(d->K);
+  const int ksb = variant / 10;
   a.cps = rowgemm_cps(d->M, a.nch, ksb);
   const size_t lds = (size_t)a.cps * (ksb * 2048 + 128);
   int rc;
@@ -787,9 +817,9 @@ extern "C" size_t mspi_x3d_ca_packed_bytes(int32_t D, int32_t Cx) {
   return c ? mspi_mlp_packed_bytes(c, (Cx + 31) / 32 * 32) : 0;
 }
 
-extern "C" int mspi_x3d_ca_fwd(const MspiX3dCaDesc* d, const void* u, const void* gate, const void* w_packed, const void* bc,
-                               const void* ba, const void* res, void* y, void* t, void* stream) {
-  MSPI_REQUIRE(d && u && w_packed && bc && ba && res && y && t, "mspi_x3d_ca_fwd: null argument");
+// The instantiation mspi_x3d_ca_fwd runs (include/mspi_hip.h, mspi_x3d_ca_variant): x3d_ca_kernel<C, GATE> as C * 10 + GATE;
+// -1 = a descriptor the launch refuses.  mspi_x3d_ca_fwd switches on this code.
+static int x3d_ca_select(const MspiX3dCaDesc* d, bool gate) {
   MSPI_REQUIRE(mspi_x3d_ca_supported(d->D, d->Cx), "mspi_x3d_ca_fwd: D = %d / Cx = %d outside the kernel's range", d->D, d->Cx);
   MSPI_REQUIRE(d->M >= 1 && d->M < (1L << 31), "mspi_x3d_ca_fwd: M = %ld", (long)d->M);
   MSPI_REQUIRE(d->ldu >= d->D && d->ldt >= d->D && d->ldr >= d->Cx && d->ldy >= d->Cx &&
@@ -797,6 +827,19 @@ extern "C" int mspi_x3d_ca_fwd(const MspiX3dCaDesc* d, const void* u, const void
                "mspi_x3d_ca_fwd: row strides must cover the row and be multiples of 4 floats");
   MSPI_REQUIRE(!gate || (d->rows_per_sample > 0 && d->ldg >= d->D && d->ldg % 4 == 0), "mspi_x3d_ca_fwd: gate needs rows_per_sample and ldg");
   MSPI_REQUIRE(d->wc_scale > 0.f && d->wa_scale > 0.f, "mspi_x3d_ca_fwd: weight scales must be positive");
+  return x3d_ca_c(d->D) * 10 + (gate ? 1 : 0);
+}
+
+extern "C" int mspi_x3d_ca_variant(const MspiX3dCaDesc* d, int32_t has_gate) {
+  MSPI_REQUIRE(d, "mspi_x3d_ca_variant: null descriptor");
+  return x3d_ca_select(d, has_gate != 0);
+}
+
+extern "C" int mspi_x3d_ca_fwd(const MspiX3dCaDesc* d, const void* u, const void* gate, const void* w_packed, const void* bc,
+                               const void* ba, const void* res, void* y, void* t, void* stream) {
+  MSPI_REQUIRE(d && u && w_packed && bc && ba && res && y && t, "mspi_x3d_ca_fwd: null argument");
+  const int variant = x3d_ca_select(d, gate != nullptr);
+  if (variant < 0) return variant;
   CaArgs a;
   a.u = (const float*)u; a.gate = (const float*)gate; a.wp = (const unsigned char*)w_packed; a.b1 = (const float*)bc;
   a.b2 = (const float*)ba; a.res = (const float*)res; a.y = (float*)y; a.t = (float*)t;
@@ -806,12 +849,11 @@ extern "C" int mspi_x3d_ca_fwd(const MspiX3dCaDesc* d, const void* u, const void
   a.status = g_status_word;
   const dim3 grid((unsigned)((a.M + 127) / 128));
   hipStream_t s = (hipStream_t)stream;
-  if (x3d_ca_c(d->D) == 128) {
-    if (gate) hipLaunchKernelGGL((x3d_ca_kernel<128, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((x3d_ca_kernel<128, false>), grid, dim3(256), 0, s, a);
-  } else {
-    if (gate) hipLaunchKernelGGL((x3d_ca_kernel<224, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((x3d_ca_kernel<224, false>), grid, dim3(256), 0, s, a);
+  switch (variant) {
+    case 1281: hipLaunchKernelGGL((x3d_ca_kernel<128, true>), grid, dim3(256), 0, s, a); break;
+    case 1280: hipLaunchKernelGGL((x3d_ca_kernel<128, false>), grid, dim3(256), 0, s, a); break;
+    case 2241: hipLaunchKernelGGL((x3d_ca_kernel<224, true>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((x3d_ca_kernel<224, false>), grid, dim3(256), 0, s, a); break;
   }
   return check_launch("mspi_x3d_ca_fwd");
 }

@@ -267,16 +267,30 @@ extern "C" size_t mspi_x3d_ab_packed_bytes(int32_t Cin, int32_t Cmid) {
   return (size_t)((Cmid + 31) / 32) * x3d_ks(Cin) * 4096;
 }
 
-extern "C" int mspi_x3d_ab_fwd(const MspiX3dAbDesc* d, const void* x, const void* wa_packed, const void* bias_a, const void* wb,
-                               const void* bias_b, void* u, void* pool, void* stream) {
-  MSPI_REQUIRE(d && x && wa_packed && bias_a && wb && bias_b && u, "mspi_x3d_ab_fwd: null argument");
+// The instantiation mspi_x3d_ab_fwd runs (include/mspi_hip.h, mspi_x3d_ab_variant): x3d_ab_kernel<KS, TH, TW, SL> as
+// KS * 10000 + TH * 1000 + TW * 10 + SL; -1 = a descriptor the launch refuses.  mspi_x3d_ab_fwd switches on this code.
+static int x3d_ab_select(const MspiX3dAbDesc* d) {
   MSPI_REQUIRE(mspi_x3d_ab_supported(d), "mspi_x3d_ab_fwd: shape N=%d T=%d H=%d W=%d Cin=%d Cmid=%d is outside the fused kernel's range",
                d->N, d->T, d->H, d->W, d->Cin, d->Cmid);
   MSPI_REQUIRE(d->N >= 1 && d->N < 65536 && d->ldx >= d->Cin && d->ldu >= d->Cmid && d->ldx % 4 == 0 && d->ldu % 4 == 0,
                "mspi_x3d_ab_fwd: row strides must cover the row and be multiples of 4 floats");
-  MSPI_REQUIRE(aligned16(x) && aligned16(u) && aligned16(wb) && aligned16(bias_b) && aligned16(wa_packed), "mspi_x3d_ab_fwd: 16-byte alignment");
   MSPI_REQUIRE(d->act == MSPI_ACT_NONE || d->act == MSPI_ACT_SWISH, "mspi_x3d_ab_fwd: act must be NONE or SWISH");
   MSPI_REQUIRE(d->wa_scale > 0.f, "mspi_x3d_ab_fwd: wa_scale must be positive");
+  const int ks = x3d_ks(d->Cin);
+  return d->W % 14 == 0 ? ks * 10000 + 7142 : ks * 10000 + 7071;
+}
+
+extern "C" int mspi_x3d_ab_variant(const MspiX3dAbDesc* d) {
+  MSPI_REQUIRE(d, "mspi_x3d_ab_variant: null descriptor");
+  return x3d_ab_select(d);
+}
+
+extern "C" int mspi_x3d_ab_fwd(const MspiX3dAbDesc* d, const void* x, const void* wa_packed, const void* bias_a, const void* wb,
+                               const void* bias_b, void* u, void* pool, void* stream) {
+  MSPI_REQUIRE(d && x && wa_packed && bias_a && wb && bias_b && u, "mspi_x3d_ab_fwd: null argument");
+  const int variant = x3d_ab_select(d);
+  if (variant < 0) return variant;
+  MSPI_REQUIRE(aligned16(x) && aligned16(u) && aligned16(wb) && aligned16(bias_b) && aligned16(wa_packed), "mspi_x3d_ab_fwd: 16-byte alignment");
   X3dAbArgs a;
   a.x = (const float*)x; a.wa = (const unsigned char*)wa_packed; a.ba = (const float*)bias_a; a.wb = (const float*)wb;
   a.bb = (const float*)bias_b; a.u = (float*)u; a.pool = (float*)pool;
@@ -289,20 +303,14 @@ extern "C" int mspi_x3d_ab_fwd(const MspiX3dAbDesc* d, const void* x, const void
   x3d_geometry(d, a);
   if (tseg_env > 0 && !pool) { a.tseg = tseg_env; a.nseg = (d->T + a.tseg - 1) / a.tseg; }
   hipStream_t s = (hipStream_t)stream;
-  const int ks = x3d_ks(d->Cin);
-  if (d->W % 14 == 0) {
-    switch (ks) {
-      case 1: launch_ab<1, 7, 14, 2>(a, s); break;
-      case 2: launch_ab<2, 7, 14, 2>(a, s); break;
-      default: launch_ab<3, 7, 14, 2>(a, s); break;
-    }
-  } else {
-    switch (ks) {
-      case 1: launch_ab<1, 7, 7, 1>(a, s); break;
-      case 2: launch_ab<2, 7, 7, 1>(a, s); break;
-      case 3: launch_ab<3, 7, 7, 1>(a, s); break;
-      default: launch_ab<6, 7, 7, 1>(a, s); break;
-    }
+  switch (variant) {
+    case 17142: launch_ab<1, 7, 14, 2>(a, s); break;
+    case 27142: launch_ab<2, 7, 14, 2>(a, s); break;
+    case 37142: launch_ab<3, 7, 14, 2>(a, s); break;
+    case 17071: launch_ab<1, 7, 7, 1>(a, s); break;
+    case 27071: launch_ab<2, 7, 7, 1>(a, s); break;
+    case 37071: launch_ab<3, 7, 7, 1>(a, s); break;
+    default: launch_ab<6, 7, 7, 1>(a, s); break;
   }
   return check_launch("mspi_x3d_ab_fwd");
 }

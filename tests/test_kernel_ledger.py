@@ -72,13 +72,17 @@ for _D, _Dv in _PAIRS:
 # MSPI_ATTN_KSPLIT=0 only drops the merge pass (codes above); MSPI_ATTN_PLANES=0 (engine) only routes f16x3 to kind 2.
 
 
-def _switches():
-    return sorted(k for k in os.environ if k.startswith("MSPI_DW_") or k.startswith("MSPI_ATTN_"))
+# environment switches that move calls between the kernels of this ledger (test_gemm_ledger.py passes its own prefixes)
+SWITCHES = ("MSPI_DW_", "MSPI_ATTN_")
 
 
-def _no_switches():
-    if _switches():
-        pytest.skip("dispatch switches set in the environment: %s" % ", ".join(_switches()))
+def _switches(prefixes=SWITCHES):
+    return sorted(k for k in os.environ if k.startswith(prefixes))
+
+
+def _no_switches(prefixes=SWITCHES):
+    if _switches(prefixes):
+        pytest.skip("dispatch switches set in the environment: %s" % ", ".join(_switches(prefixes)))
 
 
 def _dw_desc(N, Cc, T, H, W, k, s, p, ldx=None, ldy=None):
