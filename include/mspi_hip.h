@@ -428,6 +428,40 @@ int mspi_x3d_ca_variant(const MspiX3dCaDesc* d, int32_t has_gate);
 int mspi_saliency_metrics(const float* pred, const float* gt, const float* fix, float* out /*[N][4]*/, int32_t N, int32_t L,
                           int32_t pred_is_log, mspi_stream_t stream);
 
+/* AUC-Judd (utils/compute_saliency_metrics.py:111-203, a port of the MIT benchmark's AUC_Judd), one score per map.
+ * sal holds N maps of L values, float (is_f64 = 0: the reference's jitter=False arithmetic) or double (is_f64 = 1: the
+ * caller has added the jitter noise, :150, which promotes the map to float64 upstream); fix is the fixation map
+ * (a pixel is a fixation where fix > 0).  Per map: min-max normalisation with an IEEE division in the map's own type
+ * (:153-154), the normalised values at the n fixations sorted descending as thresholds (:164-168),
+ * above[i] = #{S >= thresh[i]} over all L pixels as integer counts (:176), tp / fp in float64 (:177-179) and the
+ * trapezoid of tp over fp (:182).  score[m] is NaN for a map without fixations (:133-136) or a constant map (0/0
+ * everywhere, :156-159); nfix[m] = n.  Any n is accepted; n = L divides by zero as upstream does.  Three launches
+ * (range + compaction + sort; the pixel pass over several workgroups per map; scan + trapezoid), integer atomics
+ * only: bitwise reproducible.  ws: mspi_saliency_auc_ws_bytes(N, L) bytes of device scratch, 16-byte aligned. */
+size_t mspi_saliency_auc_ws_bytes(int32_t N, int32_t L);
+int mspi_saliency_auc_judd(const void* sal, int32_t is_f64, const float* fix, double* score /*[N]*/, int32_t* nfix /*[N]*/,
+                           void* ws, int32_t N, int32_t L, mspi_stream_t stream);
+
+/* The device part of shuffled AUC (utils/compute_saliency_metrics.py:206-276): per map of H x W floats, after the float32
+ * min-max normalisation of normalize_map (:33-43, IEEE division), with th_k = (float)(k / 10), k = 1..9 (numpy compares a
+ * float32 array with a Python float in float32):
+ *   counts[m][k-1]     = #{ (s >= th_k ? 1 : 0) + gt == 2 }                        (:258-260)
+ *   counts[m][9 + k-1] = #{ other-fixations whose looked-up value r > th_k }       (:265)
+ *   counts[m][18]      = #{ gt == 1 }   (sum(gt) of a binary map, :221)
+ *   counts[m][19]      = #{ other == 1 }                                           (:223-227)
+ * An other-fixation at (row, col) is encoded as k = row * H + col (:226, H not W) and read back as
+ * s[k % H - 1][k / H] with row -1 wrapping to H - 1 (:246); that stays inside the map only for H <= W, so H > W is
+ * refused (upstream raises IndexError).  Every split of the reference permutes ALL other-fixations and only counts, so
+ * the splits are equal and one evaluation suffices; round(x, 4), the sort of the 11 points and the trapezoid
+ * (:267-274) are a few float64 operations on these counts and are the host's. */
+int mspi_saliency_sauc_counts(const float* sal, const float* gt, const float* other, int32_t* counts /*[N][20]*/, int32_t N,
+                              int32_t H, int32_t W, mspi_stream_t stream);
+
+/* Information gain over a baseline map (utils/compute_saliency_metrics.py:278-308): per map, with every map divided by
+ * its own sum, out[m] = sum(gt * (log(eps + pred) - log(eps + base))), eps = 2.2204e-16.  Batch means are the caller's. */
+int mspi_saliency_ig(const float* pred, const float* gt, const float* base, float* out /*[N]*/, int32_t N, int32_t L,
+                     mspi_stream_t stream);
+
 /* MorphMLP token regrouping (backbones/MorphMLP.py:49-58,87-100,134-137: the reshape/permute/reshape chains around
  * mlp_h / mlp_w / mlp_t) as ONE strided gather: y is dense with extents dims[0..5] (dims[5] innermost),
  * y[i0..i5] = x[sum_k i_k * strides[k]]; strides[5] must be 1, src_elems bounds the reads. */
