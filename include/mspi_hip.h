@@ -170,6 +170,11 @@ int mspi_dwconv_variant(const MspiDwConvDesc* d);
 int mspi_se_gate(const float* pool, int32_t rows, float inv_count, const float* w1, const float* b1,
                  const float* w2, const float* b2, float* gate, int32_t N, int32_t C, int32_t F,
                  mspi_stream_t stream);
+/* Which instantiation mspi_se_gate launches for C channels and F hidden units (host only, no GPU call):
+ * 1 = se_gate_kernel<true> (C <= 512 and F <= 32: both weight matrices preloaded into registers), 2 = se_gate_kernel<false>
+ * (generic loops); -1 = an extent the launch refuses (C or F <= 0, or [G*C | C | F] floats beyond the 64 KB of LDS).
+ * mspi_se_gate selects its kernel by this same function. */
+int mspi_se_gate_variant(int32_t C, int32_t F);
 
 /* ------------------------------------------------------------------------------------
  * LayerNorm over the C columns of each row, one wavefront per row:
@@ -184,6 +189,11 @@ int mspi_se_gate(const float* pool, int32_t rows, float inv_count, const float* 
 int mspi_layernorm_fwd(const float* x, int64_t ldx, int64_t sNx, float* y, int64_t ldy, int64_t sNy,
                        const float* gamma, const float* beta, float eps, int32_t N, int32_t R, int32_t C,
                        int32_t act, const float* table /*NULL or [R][C]*/, mspi_stream_t stream);
+/* Which instantiation mspi_layernorm_fwd (planes_out = 0) / mspi_layernorm_sp_fwd (planes_out = 1) launches for rows of C
+ * floats (host only, no GPU call): LPR * 100 + VPT of layernorm_kernel<LPR, VPT> -- LPR lanes per row, VPT float4 per lane --
+ * 1601 (C <= 64), 1602 (<= 128), 1604 (<= 256), 3204 (<= 512), 6404 (<= 1024), 6408 (<= 2048), 6412 (<= 3072); -1 = a width
+ * the launch refuses (C % 4 != 0, C > 3072, planes_out with C % 32 != 0).  The launch selects its kernel by this same function. */
+int mspi_layernorm_variant(int32_t C, int32_t planes_out);
 
 /* ------------------------------------------------------------------------------------
  * Fused multi-head attention (flash style, MFMA, online softmax, fp32 in / fp32 accumulate):
@@ -334,7 +344,8 @@ int mspi_neg_cosine(const float* p, const float* z, float* out, int32_t N, int32
 
 /* Saliency-map post-processing (inference.py:66-69,85-89; OpenCV upstream -- parity unpinned):
  * out[n] = uint8( round( 255 * minmax( resize_bilinear( exp( GaussianBlur11x11(logmap[n]) ), Ho x Wo ) ) ) ).
- * workspace: mspi_postprocess_workspace(...) bytes of device memory. */
+ * workspace: mspi_postprocess_workspace(...) bytes of device memory.  H, W >= 6: the blur reflects once, and for a map smaller
+ * than its radius no reference defines the result (refused). */
 size_t mspi_postprocess_workspace(int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo);
 int mspi_postprocess_u8(const float* logmap, unsigned char* out, void* workspace, int32_t N, int32_t H, int32_t W,
                         int32_t Ho, int32_t Wo, mspi_stream_t stream);
@@ -471,6 +482,10 @@ typedef struct MspiPermuteDesc {
   int64_t src_elems;
 } MspiPermuteDesc;
 int mspi_permute_fwd(const MspiPermuteDesc* d, const float* x, float* y, mspi_stream_t stream);
+/* Which instantiation mspi_permute_fwd launches (host only, no GPU call; x and y are only inspected for alignment):
+ * 4 = 16-byte vectors (dims[5] % 4 == 0, strides[0..4] % 4 == 0, both pointers 16-byte aligned), 1 = scalar; -1 = a
+ * descriptor the launch refuses.  mspi_permute_fwd selects its kernel by this same function. */
+int mspi_permute_variant(const MspiPermuteDesc* d, const float* x, const float* y);
 
 /* MorphFC re-weighting (backbones/MorphMLP.py:64-67,104-107): y[n,r,c] = sum_j softmax_j(logit[n, c*J + j]) * src_j[n,r,c]
  * over dense [N, rows_per_sample, C] operands; J = 3 (a, b, c) or 2 (a, b; c may be NULL). */

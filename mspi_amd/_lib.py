@@ -122,6 +122,8 @@ _SIGNATURES = {
     "mspi_dwconv_pool_rows": (C.c_int, [C.POINTER(DwConvDesc)]),
     "mspi_dwconv_variant": (C.c_int, [C.POINTER(DwConvDesc)]),
     "mspi_se_gate": (C.c_int, [_P, C.c_int32, C.c_float, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mspi_se_gate_variant": (C.c_int, [C.c_int32, C.c_int32]),
+    "mspi_layernorm_variant": (C.c_int, [C.c_int32, C.c_int32]),
     "mspi_layernorm_fwd": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mspi_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -142,6 +144,7 @@ _SIGNATURES = {
     "mspi_neg_cosine": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
     "mspi_add": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "mspi_permute_fwd": (C.c_int, [C.POINTER(PermuteDesc), _P, _P, _P]),
+    "mspi_permute_variant": (C.c_int, [C.POINTER(PermuteDesc), _P, _P]),
     "mspi_gated_sum_fwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P]),
     "mspi_logspec_fwd": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     "mspi_resize_norm_fwd": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32,

@@ -69,29 +69,44 @@ __global__ __launch_bounds__(256) void gated_sum_kernel(const float* __restrict_
 
 using namespace mspi;
 
-extern "C" int mspi_permute_fwd(const MspiPermuteDesc* d, const float* x, float* y, mspi_stream_t stream) {
-  MSPI_REQUIRE(d && x && y, "mspi_permute_fwd: null argument");
-  PermArgs a;
-  a.x = x; a.y = y;
+// Validates the descriptor, fills the kernel arguments and returns the instantiation (include/mspi_hip.h,
+// mspi_permute_variant): 4 = permute_kernel<4> (16-B vectors), 1 = permute_kernel<1>; MSPI_EINVAL (error text set) for a
+// descriptor the launch refuses.  x and y are only inspected for alignment.  The launch below switches on this code.
+static int perm_select(const MspiPermuteDesc* d, const float* x, const float* y, PermArgs& a, const char* who) {
+  MSPI_REQUIRE(d && x && y, "%s: null argument", who);
   long total = 1, span = 0;
   for (int k = 0; k < 6; ++k) {
-    MSPI_REQUIRE(d->dims[k] > 0 && d->strides[k] >= 0, "mspi_permute_fwd: dims[%d]=%d strides[%d]=%ld", k, d->dims[k], k,
+    MSPI_REQUIRE(d->dims[k] > 0 && d->strides[k] >= 0, "%s: dims[%d]=%d strides[%d]=%ld", who, k, d->dims[k], k,
                  (long)d->strides[k]);
     a.d[k] = d->dims[k]; a.s[k] = d->strides[k];
     total *= d->dims[k];
     span += (long)(d->dims[k] - 1) * d->strides[k];
   }
   // the gather must stay inside the source buffer the caller declares
-  MSPI_REQUIRE(span < d->src_elems, "mspi_permute_fwd: strides reach element %ld of a %ld-element source", span,
+  MSPI_REQUIRE(span < d->src_elems, "%s: strides reach element %ld of a %ld-element source", who, span,
                (long)d->src_elems);
-  MSPI_REQUIRE(d->strides[5] == 1, "mspi_permute_fwd: the innermost run must be contiguous (stride 1)");
+  MSPI_REQUIRE(d->strides[5] == 1, "%s: the innermost run must be contiguous (stride 1)", who);
   bool v4 = (d->dims[5] & 3) == 0 && aligned16(x) && aligned16(y);
   for (int k = 0; k < 5; ++k) v4 = v4 && (d->strides[k] & 3) == 0;
   if (v4) { a.d[5] >>= 2; total >>= 2; }
   a.total = total;
-  MSPI_REQUIRE((total + 255) / 256 < (1L << 31), "mspi_permute_fwd: grid too large");
-  const dim3 grid((unsigned)((total + 255) / 256));
-  if (v4) hipLaunchKernelGGL(permute_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  MSPI_REQUIRE((total + 255) / 256 < (1L << 31), "%s: grid too large", who);
+  return v4 ? 4 : 1;
+}
+
+extern "C" int mspi_permute_variant(const MspiPermuteDesc* d, const float* x, const float* y) {
+  PermArgs a;
+  const int v = perm_select(d, x, y, a, "mspi_permute_variant");
+  return v > 0 ? v : -1;
+}
+
+extern "C" int mspi_permute_fwd(const MspiPermuteDesc* d, const float* x, float* y, mspi_stream_t stream) {
+  PermArgs a;
+  const int variant = perm_select(d, x, y, a, "mspi_permute_fwd");
+  if (variant <= 0) return variant;
+  a.x = x; a.y = y;
+  const dim3 grid((unsigned)((a.total + 255) / 256));
+  if (variant == 4) hipLaunchKernelGGL(permute_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(permute_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("mspi_permute_fwd");
 }

@@ -139,8 +139,12 @@ extern "C" size_t mspi_postprocess_workspace(int32_t N, int32_t H, int32_t W, in
 
 extern "C" int mspi_postprocess_u8(const float* logmap, unsigned char* out, void* workspace, int32_t N, int32_t H, int32_t W,
                                    int32_t Ho, int32_t Wo, mspi_stream_t stream) {
-  MSPI_REQUIRE(logmap && out && workspace && N > 0 && H > 1 && W > 1 && Ho > 0 && Wo > 0 && N < 65536,
+  MSPI_REQUIRE(logmap && out && workspace && N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && N < 65536,
                "mspi_postprocess_u8: bad argument");
+  // the 11-tap blur reflects once: a map narrower than the radius + 1 would need repeated reflection, which OpenCV does, this
+  // kernel does not and the oracle's reflect padding refuses -- there is nothing to pin such a result to
+  MSPI_REQUIRE(H >= 6 && W >= 6, "mspi_postprocess_u8: a %d x %d map is smaller than the blur radius (H, W >= 6): no reference "
+               "defines the result", H, W);
   static bool init = false;
   if (!init) {   // cv2.getGaussianKernel(11, sigma = 0.3*((11-1)*0.5-1)+0.8 = 2.0)
     float k[11], s = 0.f;

@@ -402,32 +402,53 @@ static inline unsigned grid_for(long total) {
 
 using namespace mspi;
 
+// The instantiation for a row of C floats (include/mspi_hip.h, mspi_layernorm_variant): LPR * 100 + VPT, chosen by the number
+// of float4 per row; 0 = no instantiation holds the row.  The launch below switches on this code, so the query cannot drift
+// from what runs.
+static int ln_select(int32_t C) {
+  const int nv = C / 4;
+  if (nv <= 16) return 1601;
+  if (nv <= 32) return 1602;
+  if (nv <= 64) return 1604;
+  if (nv <= 128) return 3204;
+  if (nv <= 256) return 6404;
+  if (nv <= 512) return 6408;
+  if (nv <= LN_MAXC / 4) return 6412;
+  return 0;
+}
+
+static bool ln_width_ok(int32_t C) { return C > 0 && (C & 3) == 0 && C <= LN_MAXC; }
+
+extern "C" int mspi_layernorm_variant(int32_t C, int32_t planes_out) {
+  if (!ln_width_ok(C)) { set_error("mspi_layernorm_variant: C=%d must be a multiple of 4, <= %d", C, LN_MAXC); return -1; }
+  if (planes_out && (C & 31) != 0) { set_error("mspi_layernorm_variant: blocked output planes need C %% 32 == 0 (C=%d)", C); return -1; }
+  return ln_select(C);
+}
+
 static int layernorm_impl(const float* x, int64_t ldx, int64_t sNx, float* y, int64_t ldy, int64_t sNy, void* planes, int64_t ldo,
                           int64_t plane, const float* gamma, const float* beta, float eps, int32_t N, int32_t R, int32_t C,
                           int32_t act, const float* table, mspi_stream_t stream, const char* who) {
   MSPI_REQUIRE(x && (y || planes) && gamma && beta, "%s: null argument", who);
   const int64_t M = (int64_t)N * R;
   MSPI_REQUIRE(M < (1L << 31), "%s: more than 2^31 rows", who);
-  MSPI_REQUIRE(N > 0 && R > 0 && C > 0 && (C & 3) == 0 && C <= LN_MAXC, "%s: C=%d must be a multiple of 4, <= %d", who, C, LN_MAXC);
+  MSPI_REQUIRE(N > 0 && R > 0 && ln_width_ok(C), "%s: C=%d must be a multiple of 4, <= %d", who, C, LN_MAXC);
   MSPI_REQUIRE((ldx & 3) == 0 && ldx >= C && (sNx & 3) == 0, "%s: bad input row/sample stride", who);
   MSPI_REQUIRE(planes || ((ldy & 3) == 0 && ldy >= C && (sNy & 3) == 0 && aligned16(y)), "%s: bad output row/sample stride", who);
   MSPI_REQUIRE(!planes || ((C & 31) == 0 && ldo == C && plane >= (M + 15) / 16 * 16 * ldo && (plane & 7) == 0 && aligned16(planes)),
                "%s: blocked output planes need C %% 32 == 0, ld == C and plane >= roundup16(M)*C", who);
   MSPI_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(beta) && (!table || aligned16(table)), "%s: pointers must be 16-B aligned", who);
   MSPI_REQUIRE(M < (1L << 31), "%s: too many rows", who);
-  const int nv = C / 4;
   hipStream_t s = (hipStream_t)stream;
 #define MSPI_LN(LPR, VPT)                                                                                             \
-  hipLaunchKernelGGL((layernorm_kernel<LPR, VPT>), dim3((unsigned)((M + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)))), dim3(256), \
-                     0, s, x, (long)ldx, (long)sNx, y, (long)ldy, (long)sNy, gamma, beta, eps, (long)M, R, C, act, table,    \
-                     (_Float16*)planes, (long)ldo, (long)plane)
-  if (nv <= 16) MSPI_LN(16, 1);
-  else if (nv <= 32) MSPI_LN(16, 2);
-  else if (nv <= 64) MSPI_LN(16, 4);
-  else if (nv <= 128) MSPI_LN(32, 4);
-  else if (nv <= 256) MSPI_LN(64, 4);
-  else if (nv <= 512) MSPI_LN(64, 8);
-  else MSPI_LN(64, 12);
+  case LPR * 100 + VPT:                                                                                               \
+    hipLaunchKernelGGL((layernorm_kernel<LPR, VPT>), dim3((unsigned)((M + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)))), dim3(256), \
+                       0, s, x, (long)ldx, (long)sNx, y, (long)ldy, (long)sNy, gamma, beta, eps, (long)M, R, C, act, table,    \
+                       (_Float16*)planes, (long)ldo, (long)plane);                                                    \
+    break;
+  switch (ln_select(C)) {
+    MSPI_LN(16, 1) MSPI_LN(16, 2) MSPI_LN(16, 4) MSPI_LN(32, 4) MSPI_LN(64, 4) MSPI_LN(64, 8) MSPI_LN(64, 12)
+    default: MSPI_REQUIRE(false, "%s: no kernel for C=%d", who, C);
+  }
 #undef MSPI_LN
   return check_launch(who);
 }
@@ -446,14 +467,33 @@ extern "C" int mspi_layernorm_sp_fwd(const float* x, int64_t ldx, int64_t sNx, v
                         "mspi_layernorm_sp_fwd");
 }
 
+// The instantiation for a gate of C channels and F hidden units (include/mspi_hip.h, mspi_se_gate_variant): 1 =
+// se_gate_kernel<true> (register-preloaded weights), 2 = se_gate_kernel<false>, 0 = the [G*C | C | F] floats exceed the LDS.
+// The launch below switches on this code.
+static size_t se_lds_bytes(int32_t C, int32_t F) {
+  const int G = C <= 1024 ? 1024 / C : 1;
+  return ((size_t)G * C + (size_t)C + (size_t)F) * sizeof(float);
+}
+
+static int se_select(int32_t C, int32_t F) {
+  if (C <= 0 || F <= 0 || se_lds_bytes(C, F) > 64 * 1024) return 0;
+  return (C <= 512 && F <= 32) ? 1 : 2;
+}
+
+extern "C" int mspi_se_gate_variant(int32_t C, int32_t F) {
+  const int v = se_select(C, F);
+  if (!v) { set_error("mspi_se_gate_variant: bad extent C=%d F=%d", C, F); return -1; }
+  return v;
+}
+
 extern "C" int mspi_se_gate(const float* pool, int32_t rows, float inv_count, const float* w1, const float* b1,
                             const float* w2, const float* b2, float* gate, int32_t N, int32_t C, int32_t F,
                             mspi_stream_t stream) {
   MSPI_REQUIRE(pool && w1 && b1 && w2 && b2 && gate, "mspi_se_gate: null argument");
-  const int G = C <= 1024 ? 1024 / C : 1;
-  const size_t lds = (size_t)(G * C + C + F) * sizeof(float);
-  MSPI_REQUIRE(N > 0 && rows > 0 && C > 0 && F > 0 && lds <= 64 * 1024, "mspi_se_gate: bad extent");
-  if (C <= 512 && F <= 32) hipLaunchKernelGGL((se_gate_kernel<true>), dim3(N), dim3(1024), lds, (hipStream_t)stream, pool, rows, inv_count, w1, b1, w2,
+  const int variant = se_select(C, F);
+  MSPI_REQUIRE(N > 0 && rows > 0 && variant, "mspi_se_gate: bad extent");
+  const size_t lds = se_lds_bytes(C, F);
+  if (variant == 1) hipLaunchKernelGGL((se_gate_kernel<true>), dim3(N), dim3(1024), lds, (hipStream_t)stream, pool, rows, inv_count, w1, b1, w2,
                      b2, gate, C, F);
   else hipLaunchKernelGGL((se_gate_kernel<false>), dim3(N), dim3(1024), lds, (hipStream_t)stream, pool, rows, inv_count, w1, b1, w2,
                      b2, gate, C, F);
