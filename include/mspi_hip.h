@@ -473,6 +473,24 @@ int mspi_saliency_sauc_counts(const float* sal, const float* gt, const float* ot
 int mspi_saliency_ig(const float* pred, const float* gt, const float* base, float* out /*[N]*/, int32_t N, int32_t L,
                      mspi_stream_t stream);
 
+/* Bilinear resize of N maps [H][W] -> [Ho][Wo], what upstream does with cv2.resize(..., INTER_LINEAR default) when it brings
+ * the prediction to the fixation map's size (utils/compute_saliency_metrics.py:119-122) and the density to the model's size
+ * (avsp_dataloader.py:176).  src is uint8 (src_is_u8 != 0: a decoded image, values used as 0..255, unscaled) or float; dst is
+ * float.  Pixel centres aligned, src = (dst + 0.5) * in / out - 0.5, edges clamped, no antialiasing when shrinking.  The
+ * source index and its fractional weight are exact integer arithmetic, the weight rounded once to fp32; the arithmetic on
+ * the samples is fp32 (at most 13 roundings per output, each <= 2^-24 max|src|).  Ho == H && Wo == W copies (converts) bit
+ * for bit.  One launch, 16-byte stores; extents up to 2^23.  Parity with OpenCV's own fixed-point path is not pinned. */
+int mspi_resize_bilinear_fwd(const void* src, int32_t src_is_u8, float* dst, int32_t N, int32_t H, int32_t W, int32_t Ho,
+                             int32_t Wo, mspi_stream_t stream);
+
+/* resize_fixation (avsp_dataloader.py:16-31) for N fixation maps [H][W] -> [row][col]: every non-zero input pixel (r, c) sets
+ * dst[min(rint(r * (row / H)), row - 1)][min(rint(c * (col / W)), col - 1)] = 1, everything else is 0.  The ratio is the
+ * float64 quotient the reference forms first (:18-19), the product float64, the rounding half to even (np.round, :23-24):
+ * equal to the reference bit for bit, shrinking, enlarging or identity.  Two launches on `stream`: a zero fill of dst, then
+ * stores of the constant 1.0f from the non-zero inputs (sources that share a target write the same value). */
+int mspi_resize_fixation_fwd(const float* fix, float* dst, int32_t N, int32_t H, int32_t W, int32_t row, int32_t col,
+                             mspi_stream_t stream);
+
 /* MorphMLP token regrouping (backbones/MorphMLP.py:49-58,87-100,134-137: the reshape/permute/reshape chains around
  * mlp_h / mlp_w / mlp_t) as ONE strided gather: y is dense with extents dims[0..5] (dims[5] innermost),
  * y[i0..i5] = x[sum_k i_k * strides[k]]; strides[5] must be 1, src_elems bounds the reads. */
