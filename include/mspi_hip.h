@@ -528,6 +528,25 @@ int mspi_resize_norm_fwd(const unsigned char* rgb, int32_t Hin, int32_t Win, uns
                          int32_t hks, const int32_t* vb, const int32_t* vk, int32_t vks, const float* mean3_host,
                          const float* std3_host, mspi_stream_t stream);
 
+/* Clip assembly: N decoded frames of ONE source size -> their slots of a fp32 [B][3][T][Hout][Wout] clip tensor, the
+ * arithmetic of mspi_resize_norm_fwd (bit for bit) in one launch, without a scratch buffer: a workgroup stages the
+ * horizontally resampled rows its output tile taps in LDS and runs the vertical pass from there.  frames: uint8
+ * [N][Hin][Win][3], packed, 4-byte aligned, on the device; slots [N]: frame i goes to out[b][:][t] with b * T + t = slots[i]
+ * (device table; slots_host is the same table on the host: every slot is checked to be < B * T and written once before the
+ * launch); element (b, c, t, y, x) of out is at b * sB + c * sC + t * sT + y * sH + x floats.  hb / hk / vb / vk: as for
+ * mspi_resize_norm_fwd; hb_host / vb_host: host copies of the two bounds tables (checked against Win / Hin, and the tile
+ * height is planned from vb_host).  Returns MSPI_EINVAL without launching where no tile fits the LDS budget
+ * (mspi_clip_resize_plan tells in advance); the caller then runs mspi_resize_norm_fwd per frame.
+ * mspi_clip_resize_plan (host only): plan4 = { output rows per tile, staged rows per tile (tile k stages the input rows
+ * [vb[k * TH][0], + staged)), input rows per load batch, LDS bytes per workgroup }. */
+int mspi_clip_resize_plan(const int32_t* vb_host, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout, int32_t vks,
+                          int32_t* plan4);
+int mspi_clip_resize_norm_fwd(const unsigned char* frames, int32_t N, int32_t Hin, int32_t Win, const int32_t* slots,
+                              const int32_t* slots_host, float* out, int32_t B, int32_t T, int64_t sB, int64_t sC, int64_t sT,
+                              int64_t sH, int32_t Hout, int32_t Wout, const int32_t* hb, const int32_t* hb_host,
+                              const int32_t* hk, int32_t hks, const int32_t* vb, const int32_t* vb_host, const int32_t* vk,
+                              int32_t vks, const float* mean3_host, const float* std3_host, mspi_stream_t stream);
+
 /* Pre-split activations.  The f16x3 GEMM computes x*w from f16 hi/lo halves of both operands; the weights are split at pack
  * time, and a producer may hand the activations over ALREADY split: two f16 planes (hi plane, lo plane `plane` elements
  * later; hi = f16(x), lo = f16(x - hi) -- the same split the kernels otherwise do in registers, so results are

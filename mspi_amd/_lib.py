@@ -149,6 +149,10 @@ _SIGNATURES = {
     "mspi_logspec_fwd": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     "mspi_resize_norm_fwd": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32,
                                         _P, _P, C.c_int32, _P, _P, _P]),
+    "mspi_clip_resize_plan": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mspi_clip_resize_norm_fwd": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64,
+                                             C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P,
+                                             _P, C.c_int32, _P, _P, _P]),
     "mspi_layernorm_sp_fwd": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, _P]),
     "mspi_split_planes_fwd": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P]),

@@ -92,3 +92,66 @@ def log_spectrogram(wave, segments, Wa=111):
     check(lib.mspi_logspec_fwd(wave.data_ptr(), wave.numel(), seg.data_ptr(), seg_host.ctypes.data, B, _WINDOW[str(dev)].data_ptr(),
                                out.data_ptr(), Wa, torch.cuda.current_stream().cuda_stream), "mspi_logspec_fwd")
     return out
+
+
+_COEFFS_HOST = {}
+
+
+def _coeffs_host(in_size, out_size):
+    key = (in_size, out_size)
+    if key not in _COEFFS_HOST:
+        b, _, ks = pil_bilinear_coeffs(in_size, out_size)
+        _COEFFS_HOST[key] = (np.ascontiguousarray(b), ks)
+    return _COEFFS_HOST[key]
+
+
+def clip_tile_plan(Hin, Win, Hout, Wout):
+    """What one workgroup of mspi_clip_resize_norm_fwd stages for frames Hin x Win -> Hout x Wout, planned on the host from
+    the vertical bounds table: {"tile_rows", "staged_rows", "batch_rows", "lds_bytes"}, or None where no tile fits the LDS
+    budget (extreme shrink factors, very wide frames).  No GPU call."""
+    lib = _lib.load()
+    vb, vks = _coeffs_host(Hin, Hout)
+    plan = (C.c_int32 * 4)()
+    if lib.mspi_clip_resize_plan(vb.ctypes.data, Hin, Win, Hout, Wout, vks, plan) != 0:
+        return None
+    return {"tile_rows": plan[0], "staged_rows": plan[1], "batch_rows": plan[2], "lds_bytes": plan[3]}
+
+
+def assemble_clips(frames_u8, slots, out, mean, std, slots_dev=None):
+    """frames_u8: uint8 [N, Hin, Win, 3] on the GPU (N decoded frames of one source size); out: fp32 [B, 3, T, Hout, Wout]
+    on the GPU; slots: N integers, frame i is written to out[b, :, t] with b * T + t = slots[i].  Each frame gets
+    resize_normalize's result (PIL bilinear resize bit for bit, /255, -mean, /std) straight in its slot: one launch for
+    the N frames, no temporary.  Slots that are not named keep what they held.  slots_dev: the same table as an int32 CUDA
+    tensor, for callers that may not allocate (graph capture); built here otherwise.  Where no tile of the batched kernel
+    fits (clip_tile_plan() is None) the frames go through resize_normalize one by one.  Returns out."""
+    lib = _lib.load()
+    if not (frames_u8.is_cuda and out.is_cuda):
+        raise MspiError("assemble_clips runs on the GPU only (tensors on %s, %s)" % (frames_u8.device, out.device))
+    assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3 and frames_u8.is_contiguous()
+    assert out.dtype == torch.float32 and out.dim() == 5 and out.shape[1] == 3 and out.stride(4) == 1
+    N, Hin, Win = frames_u8.shape[:3]
+    B, _, T, Hout, Wout = out.shape
+    slots_host = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+    if slots_host.shape[0] != N:
+        raise MspiError("assemble_clips: %d slots for %d frames" % (slots_host.shape[0], N))
+    dev = frames_u8.device
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    if N > 0 and clip_tile_plan(Hin, Win, Hout, Wout) is None:        # the per-frame path, two launches and a temporary each
+        if slots_host.min() < 0 or slots_host.max() >= B * T or np.unique(slots_host).size != N:
+            raise MspiError("assemble_clips: slots must be distinct and inside the %d x %d clip tensor" % (B, T))
+        for i, sl in enumerate(slots_host.tolist()):
+            out[sl // T, :, sl % T].copy_(resize_normalize(frames_u8[i], (Hout, Wout), mean, std))
+        return out
+    hb, hk, hks = _coeffs(Win, Wout, dev)
+    vb, vk, vks = _coeffs(Hin, Hout, dev)
+    hb_host, vb_host = _coeffs_host(Win, Wout)[0], _coeffs_host(Hin, Hout)[0]
+    if slots_dev is None:
+        slots_dev = torch.from_numpy(slots_host).to(dev)
+    assert slots_dev.dtype == torch.int32 and slots_dev.is_cuda and slots_dev.numel() == N and slots_dev.is_contiguous()
+    check(lib.mspi_clip_resize_norm_fwd(frames_u8.data_ptr(), N, Hin, Win, slots_dev.data_ptr(), slots_host.ctypes.data,
+                                        out.data_ptr(), B, T, out.stride(0), out.stride(1), out.stride(2), out.stride(3), Hout, Wout,
+                                        hb.data_ptr(), hb_host.ctypes.data, hk.data_ptr(), hks, vb.data_ptr(), vb_host.ctypes.data,
+                                        vk.data_ptr(), vks, m, s, torch.cuda.current_stream().cuda_stream),
+          "mspi_clip_resize_norm_fwd")
+    return out
