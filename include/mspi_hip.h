@@ -127,6 +127,24 @@ int mspi_conv_splitk_fwd(const MspiConvDesc* d, const float* x, const float* w, 
  * function; the weight, output and residual pointers are checked at launch only. */
 int mspi_conv_variant(const MspiConvDesc* d, const float* x, const float* gate, int32_t ksplit);
 
+/* ------------------------------------------------------------------------------------
+ * Halo-staged f16x3 implicit GEMM for stride-1 convs with kernel (kT,3,3), kT in {1,3}, pad (kT/2,1,1), on fp32
+ * channels-last input (dense or a channel slab: sC == 1, 16-B aligned pointer and strides, C % 32 == 0).  A workgroup owns
+ * an output brick of 4 x 8 x 8 (t,h,w) positions of one sample; per 32-channel chunk it stages the brick and its 1-cell
+ * halo once, split to f16 hi/lo once, into LDS and walks the taps there: only the weight block of (tap, chunk) is fetched
+ * per step.  Same descriptor and epilogue contract as mspi_conv_fwd (bias, optional residual, activation, range guard);
+ * weights are d->w_blocked (required), `tile` is ignored, no gate.  The summation order is chunk-major (fp32 accumulate).
+ * No allocation: capture safe.  A second implementation beside mspi_conv_fwd: that entry point never selects it.
+ * ------------------------------------------------------------------------------------ */
+int mspi_conv_halo_fwd(const MspiConvDesc* d, const float* x, const float* bias, const float* res, const float* gate /* must be NULL */,
+                       float* y, mspi_stream_t stream);
+/* 1 when mspi_conv_halo_fwd takes this descriptor (with a 16-B aligned input), else 0 (host only). */
+int mspi_conv_halo_supported(const MspiConvDesc* d);
+/* Which instantiation mspi_conv_halo_fwd launches: conv_halo_kernel<kT, BN / 32> as kT * 1000 + BN (BN = 64 / 128 / 192 output
+ * columns per workgroup: the smallest that holds Cout, 192 beyond); -1 = a descriptor or input pointer the launch refuses
+ * (mspi_last_error() says why).  Host only; the launch selects by this function. */
+int mspi_conv_halo_variant(const MspiConvDesc* d, const void* x);
+
 /* Which kernel instantiation the calling thread's last mspi_conv_fwd launched:
  * (BM << 16) | (BN << 4) | (8 if 8 waves) | (4 if LDS-DMA staging) | (prec << 1) | (1 if scalar gather, 0 if
  * 16-B vector gather).  For profiling: it names the template instantiation rocprofv3 reports. */
@@ -315,6 +333,16 @@ int mspi_maxpool_fwd(const MspiDwConvDesc* d, const float* x, float* y, mspi_str
 int mspi_upsample_fwd(const float* src, int64_t lds, float* dst, int64_t ldd, int32_t NT, int32_t H,
                       int32_t W, int32_t C, int32_t factor, int32_t accumulate, int32_t act,
                       mspi_stream_t stream);
+
+/* The sum of J <= 3 such up-samples in one pass over dst (the decoder's top-down fusion):
+ *   dst[n,t,ho,wo,:] = act( (dst[n,t,ho,wo,:] +) sum_j bilinear_{factors[j]}(srcs[j][n,t,:,:,:]) )
+ * srcs / lds / factors are host arrays of J entries; source j is [NT, Ho / factors[j], Wo / factors[j], C] with row
+ * stride lds[j] (every factor divides Ho and Wo).  Each term uses the arithmetic of mspi_upsample_fwd and the terms are added
+ * left to right, so the result is bit-identical to J launches of mspi_upsample_fwd(accumulate = 1) (the first with the
+ * caller's accumulate, the last with act). */
+int mspi_upsample_sum_fwd(const float* const* srcs, const int64_t* lds, const int32_t* factors, int32_t J, float* dst,
+                          int64_t ldd, int32_t NT, int32_t Ho, int32_t Wo, int32_t C, int32_t accumulate, int32_t act,
+                          mspi_stream_t stream);
 
 /* 2x2 spatial space-to-depth of Swin's PatchMerging (backbones/video_swin_transformer.py:311-326):
  * y[n,t,h,w, q*C + c] = x[n,t,2h+dh(q),2w+dw(q),c] with (dh,dw)(q) = (0,0),(1,0),(0,1),(1,1).  H, W even. */

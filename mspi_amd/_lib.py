@@ -118,6 +118,9 @@ _SIGNATURES = {
     "mspi_conv_splitk_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "mspi_conv_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
     "mspi_conv_variant": (C.c_int, [C.POINTER(ConvDesc), _P, _P, C.c_int32]),
+    "mspi_conv_halo_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
+    "mspi_conv_halo_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "mspi_conv_halo_variant": (C.c_int, [C.POINTER(ConvDesc), _P]),
     "mspi_dwconv_fwd": (C.c_int, [C.POINTER(DwConvDesc), _P, _P, _P, _P, _P, _P]),
     "mspi_dwconv_pool_rows": (C.c_int, [C.POINTER(DwConvDesc)]),
     "mspi_dwconv_variant": (C.c_int, [C.POINTER(DwConvDesc)]),
@@ -136,6 +139,8 @@ _SIGNATURES = {
     "mspi_maxpool_fwd": (C.c_int, [C.POINTER(DwConvDesc), _P, _P, _P]),
     "mspi_upsample_fwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mspi_upsample_sum_fwd": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, _P]),
     "mspi_rowgate": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
     "mspi_logsumexp_sub": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "mspi_mean_rows": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, _P]),

@@ -246,6 +246,79 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
   }
 }
 
+// ------------------------------------------------------------------ sum of up-samples (top-down fusion)
+// dst (= or +=) up_k0(src0) + up_k1(src1) + up_k2(src2) in ONE pass over dst.  Each term is evaluated with the expressions
+// of upsample_kernel and added left to right, so the result equals, bit for bit, the chain of accumulate launches it replaces.
+struct UpSumSrc {
+  const float* p;
+  long ld;
+  int H, W, k;
+};
+struct UpSumArgs {
+  UpSumSrc s[3];
+};
+
+__device__ __forceinline__ float4 upsample_tap(const UpSumSrc& s, float inv, long nt, int ho, int wo, int cv) {
+  const int H = s.H, W = s.W;
+  const long lds = s.ld;
+  float fh = ((float)ho + 0.5f) * inv - 0.5f;
+  float fw = ((float)wo + 0.5f) * inv - 0.5f;
+  fh = fh < 0.f ? 0.f : fh;
+  fw = fw < 0.f ? 0.f : fw;
+  const int h0 = (int)fh, w0 = (int)fw;
+  const int h1 = h0 + (h0 < H - 1 ? 1 : 0), w1 = w0 + (w0 < W - 1 ? 1 : 0);
+  const float lh = fh - (float)h0, lw = fw - (float)w0;
+  const float* b = s.p + (nt * H * W) * lds + cv * 4;
+  const float4 v00 = *reinterpret_cast<const float4*>(b + ((long)h0 * W + w0) * lds);
+  const float4 v01 = *reinterpret_cast<const float4*>(b + ((long)h0 * W + w1) * lds);
+  const float4 v10 = *reinterpret_cast<const float4*>(b + ((long)h1 * W + w0) * lds);
+  const float4 v11 = *reinterpret_cast<const float4*>(b + ((long)h1 * W + w1) * lds);
+  const float c00 = (1.f - lh) * (1.f - lw), c01 = (1.f - lh) * lw, c10 = lh * (1.f - lw), c11 = lh * lw;
+  float4 o;
+  o.x = c00 * v00.x + c01 * v01.x + c10 * v10.x + c11 * v11.x;
+  o.y = c00 * v00.y + c01 * v01.y + c10 * v10.y + c11 * v11.y;
+  o.z = c00 * v00.z + c01 * v01.z + c10 * v10.z + c11 * v11.z;
+  o.w = c00 * v00.w + c01 * v01.w + c10 * v10.w + c11 * v11.w;
+  return o;
+}
+
+template <int J>
+__global__ __launch_bounds__(256) void upsample_sum_kernel(UpSumArgs a, float* __restrict__ dst, long ldd, int NT, int Ho,
+                                                           int Wo, int CV, int accumulate, int act) {
+  const long total = (long)NT * Ho * Wo * CV;
+  float inv[J];
+#pragma unroll
+  for (int j = 0; j < J; ++j) inv[j] = 1.f / (float)a.s[j].k;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const unsigned ui = (unsigned)idx;      // total < 2^31, checked on the host
+    const int cv = (int)(ui % (unsigned)CV);
+    unsigned pos = ui / (unsigned)CV;
+    const int wo = (int)(pos % (unsigned)Wo);
+    pos /= (unsigned)Wo;
+    const int ho = (int)(pos % (unsigned)Ho);
+    const long nt = (long)(pos / (unsigned)Ho);
+    float* d = dst + ((nt * Ho + ho) * Wo + wo) * ldd + cv * 4;
+    float4 o = upsample_tap(a.s[0], inv[0], nt, ho, wo, cv);
+    if (accumulate) {
+      const float4 p = *reinterpret_cast<const float4*>(d);
+      o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w;
+    }
+#pragma unroll
+    for (int j = 1; j < J; ++j) {
+      const float4 u = upsample_tap(a.s[j], inv[j], nt, ho, wo, cv);
+      o.x += u.x; o.y += u.y; o.z += u.z; o.w += u.w;
+    }
+    if (act != MSPI_ACT_NONE) {
+      auto fin = [&](auto act_c) {
+        constexpr int ACT = decltype(act_c)::value;
+        o.x = act_apply(o.x, ACT); o.y = act_apply(o.y, ACT); o.z = act_apply(o.z, ACT); o.w = act_apply(o.w, ACT);
+      };
+      MSPI_DISPATCH_ACT(act, fin)
+    }
+    *reinterpret_cast<float4*>(d) = o;
+  }
+}
+
 // ------------------------------------------------------------------ PatchMerging gather (2x2 space-to-depth)
 __global__ __launch_bounds__(256) void s2d_kernel(const float* __restrict__ x, long ldx, float* __restrict__ y, long ldy,
                                                   int NT, int H, int W, int CV) {
@@ -512,6 +585,36 @@ extern "C" int mspi_upsample_fwd(const float* src, int64_t lds, float* dst, int6
   hipLaunchKernelGGL(upsample_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, (long)lds, dst,
                      (long)ldd, NT, H, W, C / 4, factor, accumulate, act);
   return check_launch("mspi_upsample_fwd");
+}
+
+extern "C" int mspi_upsample_sum_fwd(const float* const* srcs, const int64_t* lds, const int32_t* factors, int32_t J,
+                                     float* dst, int64_t ldd, int32_t NT, int32_t Ho, int32_t Wo, int32_t C,
+                                     int32_t accumulate, int32_t act, mspi_stream_t stream) {
+  MSPI_REQUIRE(srcs && lds && factors && dst, "mspi_upsample_sum_fwd: null argument");
+  MSPI_REQUIRE(J >= 1 && J <= 3, "mspi_upsample_sum_fwd: 1 to 3 sources");
+  MSPI_REQUIRE(NT > 0 && Ho > 0 && Wo > 0 && C > 0, "mspi_upsample_sum_fwd: bad extent");
+  MSPI_REQUIRE((C & 3) == 0 && (ldd & 3) == 0 && ldd >= C && aligned16(dst),
+               "mspi_upsample_sum_fwd: C/ld must be multiples of 4, pointers 16-B aligned");
+  UpSumArgs a = {};
+  for (int j = 0; j < J; ++j) {
+    const int k = factors[j];
+    MSPI_REQUIRE(k >= 1 && Ho % k == 0 && Wo % k == 0, "mspi_upsample_sum_fwd: every factor must be >= 1 and divide Ho and Wo");
+    MSPI_REQUIRE(srcs[j] && (lds[j] & 3) == 0 && lds[j] >= C && aligned16(srcs[j]),
+                 "mspi_upsample_sum_fwd: C/ld must be multiples of 4, pointers 16-B aligned");
+    a.s[j].p = srcs[j];
+    a.s[j].ld = (long)lds[j];
+    a.s[j].H = Ho / k;
+    a.s[j].W = Wo / k;
+    a.s[j].k = k;
+  }
+  const long total = (long)NT * Ho * Wo * (C / 4);
+  MSPI_REQUIRE(total < (1L << 31), "mspi_upsample_sum_fwd: more than 2^31 output vectors");
+  const dim3 grid(grid_for(total)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (J == 1) hipLaunchKernelGGL((upsample_sum_kernel<1>), grid, block, 0, st, a, dst, (long)ldd, NT, Ho, Wo, C / 4, accumulate, act);
+  else if (J == 2) hipLaunchKernelGGL((upsample_sum_kernel<2>), grid, block, 0, st, a, dst, (long)ldd, NT, Ho, Wo, C / 4, accumulate, act);
+  else hipLaunchKernelGGL((upsample_sum_kernel<3>), grid, block, 0, st, a, dst, (long)ldd, NT, Ho, Wo, C / 4, accumulate, act);
+  return check_launch("mspi_upsample_sum_fwd");
 }
 
 extern "C" int mspi_space_to_depth(const float* x, int64_t ldx, float* y, int64_t ldy, int32_t NT, int32_t H, int32_t W,

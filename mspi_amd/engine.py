@@ -23,7 +23,7 @@ import os as _os
 DEFAULT_PREC = {"f32": PREC_F32, "f16x3": PREC_F16X3}[_os.environ.get("MSPI_GEMM_PREC", "f16x3")]
 
 __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedConv", "PackedDw", "conv", "dwconv", "maxpool",
-           "layernorm", "attention", "upsample", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine",
+           "layernorm", "attention", "upsample", "upsample_sum", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine",
            "se_gate", "add", "fold_bn", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
@@ -63,6 +63,8 @@ def load_autotune(path):
 THIN = 100            # kernel choice "row-stationary thin GEMM" next to MspiConvDesc.tile codes 0..14
 SPLITK = 200          # kernel choice SPLITK + S: split-K with S slices (mspi_conv_splitk_fwd)
 SPLITK_ENABLED = _os.environ.get("MSPI_SPLITK", "1") != "0"   # A/B switch
+HALO = 300            # kernel choice "halo-staged implicit GEMM" (mspi_conv_halo_fwd): stride-1 (1|3,3,3) convs, C % 32 == 0
+HALO_ENABLED = _os.environ.get("MSPI_CONV_HALO", "1") != "0"   # A/B switch
 THIN_DEFAULT = True   # without autotuning: take the thin kernel wherever it applies
 THIN_ENABLED = _os.environ.get("MSPI_THIN", "1") != "0"   # A/B switch
 
@@ -791,9 +793,15 @@ def conv(x, pk, out=None, res=None, gate=None, act=None, tile=None, sp_out=False
         rg.act, rg.rows_per_sample, rg.w_scale = d.act, To * Ho * Wo, pk.w_scale
         rg_args = (xptr, pk.thin.data_ptr(), args[2], args[3], args[4], out.ptr, args[6])
 
+    # the halo-staged kernel (mspi_conv_halo_fwd) is a second implementation of stride-1 (1|3,3,3) convs: kernel choice HALO
+    halo = bool(HALO_ENABLED and gate is None and d.w_blocked and pk.k[1:] == (3, 3) and xptr % 16 == 0 and
+                lib.mspi_conv_halo_supported(C.byref(d)))
+
     def launch(t):
         if t == THIN:
             return lib.mspi_rowgemm_fwd(C.byref(rg), *rg_args)
+        if t == HALO:
+            return lib.mspi_conv_halo_fwd(C.byref(d), args[0], args[2], args[3], None, out.ptr, args[6])
         if t >= SPLITK:      # split-K: t - SPLITK slices of the contraction, partial sums through a scratch buffer
             S = t - SPLITK
             ws = torch.empty(S * M * pk.cout_s, dtype=torch.float32, device=dev)   # stream-ordered: safe to drop after the launch
@@ -803,7 +811,7 @@ def conv(x, pk, out=None, res=None, gate=None, act=None, tile=None, sp_out=False
         return lib.mspi_conv_fwd(C.byref(d), *args)
 
     choice = -1
-    key = (M, taps * pk.cin_s, pk.cout_s, pk.k, pk.stride, pk.prec, d.sC == 1, res is not None, gate is not None, rg is not None)
+    key = (M, taps * pk.cin_s, pk.cout_s, pk.k, pk.stride, pk.prec, d.sC == 1, res is not None, gate is not None, rg is not None, halo)
     if tile is not None:
         choice = tile
     elif AUTOTUNE["on"] and not torch.cuda.is_current_stream_capturing():
@@ -816,6 +824,8 @@ def conv(x, pk, out=None, res=None, gate=None, act=None, tile=None, sp_out=False
                     cands += [12, 13, 14]        # 256-row / 8-wave form of the LDS-DMA kernel
             if rg is not None:
                 cands.append(THIN)
+            if halo:
+                cands.append(HALO)
             nk = pk.ldw // 32
             if SPLITK_ENABLED and gate is None and -(-M // 64) * -(-pk.cout_s // 64) <= 384 and nk >= 32:
                 # few output tiles, long contraction: K slices across workgroups (mspi_conv_splitk_fwd)
@@ -827,11 +837,17 @@ def conv(x, pk, out=None, res=None, gate=None, act=None, tile=None, sp_out=False
         choice = THIN
     if choice == THIN and rg is None:
         raise MspiError("conv: the thin-GEMM kernel does not cover this call")
+    if choice == HALO and not halo:
+        raise MspiError("conv: the halo-staged kernel does not cover this call")
     with tm:
-        check(launch(choice), "mspi_rowgemm_fwd" if choice == THIN else "mspi_conv_splitk_fwd" if choice >= SPLITK else "mspi_conv_fwd")
+        check(launch(choice), "mspi_rowgemm_fwd" if choice == THIN else "mspi_conv_halo_fwd" if choice == HALO else
+              "mspi_conv_splitk_fwd" if choice >= SPLITK else "mspi_conv_fwd")
         if Profiler.active is not None:
             if choice == THIN:
                 tm.name = "rowgemm<%d,f16x3>" % rowgemm_ksb(pk.cin_s)
+            elif choice == HALO:
+                v = lib.mspi_conv_halo_variant(C.byref(d), xptr)
+                tm.name = "conv_halo<%d,%d,f16x3>" % (v // 1000, v % 1000)
             elif choice >= SPLITK:
                 tm.name = "conv_gemm<64,64,splitk%d>" % (choice - SPLITK)
             else:
@@ -1162,6 +1178,24 @@ def upsample(src, factor, dst=None, accumulate=False, act=ACT_NONE):
     with _Timed("upsample", 0.0, 4.0 * (src.M + dst.M * (2 if accumulate else 1)) * src.C):
         check(lib.mspi_upsample_fwd(src.ptr, src.ld, dst.ptr, dst.ld, src.N * src.T, src.H, src.W, src.Cs, factor,
                                     1 if accumulate else 0, act, _stream()), "mspi_upsample_fwd")
+    return dst
+
+
+def upsample_sum(dst, srcs, accumulate=True, act=ACT_NONE):
+    """dst (= or +=) sum of up-samples: srcs = [(CL, integer factor), ...], at most three, in one pass over dst.
+    Bit-identical to the chain of upsample(src, k, dst=dst, accumulate=True) calls it replaces."""
+    lib = _lib.load()
+    J = len(srcs)
+    for s, k in srcs:
+        assert s.dense and s.C == dst.C and (dst.N, dst.T) == (s.N, s.T)
+        assert k >= 1 and (dst.H, dst.W) == (s.H * k, s.W * k)
+    assert dst.dense
+    ptrs = (C.c_void_p * max(J, 1))(*[s.ptr for s, _ in srcs])
+    lds = (C.c_int64 * max(J, 1))(*[s.ld for s, _ in srcs])
+    ks = (C.c_int32 * max(J, 1))(*[k for _, k in srcs])
+    with _Timed("upsample_sum", 0.0, 4.0 * (sum(s.M for s, _ in srcs) + dst.M * (2 if accumulate else 1)) * dst.C):
+        check(lib.mspi_upsample_sum_fwd(ptrs, lds, ks, J, dst.ptr, dst.ld, dst.N * dst.T, dst.H, dst.W, dst.Cs,
+                                        1 if accumulate else 0, act, _stream()), "mspi_upsample_sum_fwd")
     return dst
 
 

@@ -363,6 +363,9 @@ class _Fork:
         return False
 
 
+DECODER_FUSED = os.environ.get("MSPI_DECODER_FUSED", "1") != "0"   # A/B switch: r0 on the coarse maps, summed up-samples
+
+
 def _compose_lateral(c0, c1):
     """(s,1,1)/s conv after a 1x1x1 conv, no nonlinearity between: one conv with
     W[co,ci,tap] = sum_m W1[co,m,tap] W0[m,ci],  b[co] = sum_{tap,m} W1[co,m,tap] b0[m]."""
@@ -432,12 +435,26 @@ class _SaliencyBase(HipModule):
             "sa_cat": sa_cat,
             "lat": [self._pack_lateral(k, split if k == 3 else None) for k in range(4)],
             "r0": E.pack_conv(r[0].weight, r[0].bias),
+            "r0_parts": self._pack_r0_parts(r[0]),
             "r1": E.pack_conv(r[1].weight, r[1].bias, r[2], (1, 1, 1), (1, 1, 1), E.ACT_RELU),
             "r4": E.pack_conv(r[4].weight, r[4].bias, r[5], (1, 1, 1), (0, 1, 1), E.ACT_RELU),
             "r8": E.pack_conv(r[8].weight, r[8].bias, None, (4, 1, 1), (0, 0, 0), E.ACT_NONE),
             "r10": E.pack_conv(r[10].weight, r[10].bias, None, (1, 1, 1), (0, 1, 1), E.ACT_RELU),
             "r12": E.pack_conv(r[12].weight, r[12].bias, None, (1, 1, 1), (0, 1, 1), E.ACT_NONE),
         }
+
+    @staticmethod
+    def _r0_parts(weight, bias):
+        """The readout's 1x1x1 conv over cat(s0', up2(s1'), up4(s2'), up8(s3)) with s0' = s0 + up2(s1') + up4(s2') + up8(s3):
+        a 1x1x1 conv commutes with a per-channel bilinear up-sample, so with W = [W0|W1|W2|W3]
+        r0(cat) = W0 s0 + b + up2((W0+W1) s1') + up4((W0+W2) s2') + up8((W0+W3) s3).  Returns [(w, b)] * 4, summed in fp32."""
+        w = weight.detach().float().flatten(1)
+        d = w.shape[1] // 4
+        w0 = w[:, :d]
+        return [(w0.contiguous(), bias.detach().float())] + [((w0 + w[:, j * d:(j + 1) * d]).contiguous(), None) for j in (1, 2, 3)]
+
+    def _pack_r0_parts(self, conv):
+        return [E.pack_conv(w, b) for w, b in self._r0_parts(conv.weight, conv.bias)]
 
     def _lateral(self, pk, k, xs, out=None):
         y = E.conv(xs[0], pk["lat"][k][0])
@@ -447,7 +464,9 @@ class _SaliencyBase(HipModule):
 
     def _laterals_012(self, pk, v1, v2, v3):
         """latlayer_0..2 need only the motion encoder's first three maps: they run while the image branch is still busy.
-        s0 is produced straight into its channel slice of the readout's 768-channel input."""
+        MSPI_DECODER_FUSED=0: s0 is produced straight into its channel slice of the readout's 768-channel input."""
+        if DECODER_FUSED:
+            return None, self._lateral(pk, 0, [v1]), self._lateral(pk, 1, [v2]), self._lateral(pk, 2, [v3])
         B = v1.N
         cat = E.alloc(B, max(1, v1.T // (self.cfg.MODEL.LATERAL_STRIDE[0] if self.cfg.MODEL.LATERAL_BOOL[0] else 1)),
                       v1.H, v1.W, 4 * 192, v1.buf.device)
@@ -483,16 +502,25 @@ class _SaliencyBase(HipModule):
         self.sa_2.run(s2, masks, pm.slice(64, 32))
         E.upsample(s3, 2, dst=s2, accumulate=True)
         self.sa_1.run(s1, masks, pm.slice(32, 32))
-        E.upsample(s2, 2, dst=s1, accumulate=True)
-        E.upsample(s3, 4, dst=s1, accumulate=True)
-        self.sa_0.run(s0, masks, pm.slice(0, 32))
-        E.upsample(s1, 2, dst=s0, accumulate=True)
-        E.upsample(s2, 4, dst=s0, accumulate=True)
-        E.upsample(s3, 8, dst=s0, accumulate=True)
-        E.upsample(s1, 2, dst=cat.slice(192, 192))
-        E.upsample(s2, 4, dst=cat.slice(384, 192))
-        E.upsample(s3, 8, dst=cat.slice(576, 192))
-        y = E.conv(E.conv(E.conv(cat, pk["r0"]), pk["r1"]), pk["r4"])
+        if cat is None:
+            # r0 on the coarse maps, up-sampled after it (_r0_parts): neither s0' nor the 768-channel concat is materialised
+            E.upsample_sum(s1, [(s2, 2), (s3, 4)])
+            self.sa_0.run(s0, masks, pm.slice(0, 32))
+            p0, p1, p2, p3 = pk["r0_parts"]
+            y = E.conv(s0, p0)
+            E.upsample_sum(y, [(E.conv(s1, p1), 2), (E.conv(s2, p2), 4), (E.conv(s3, p3), 8)])
+        else:
+            E.upsample(s2, 2, dst=s1, accumulate=True)
+            E.upsample(s3, 4, dst=s1, accumulate=True)
+            self.sa_0.run(s0, masks, pm.slice(0, 32))
+            E.upsample(s1, 2, dst=s0, accumulate=True)
+            E.upsample(s2, 4, dst=s0, accumulate=True)
+            E.upsample(s3, 8, dst=s0, accumulate=True)
+            E.upsample(s1, 2, dst=cat.slice(192, 192))
+            E.upsample(s2, 4, dst=cat.slice(384, 192))
+            E.upsample(s3, 8, dst=cat.slice(576, 192))
+            y = E.conv(cat, pk["r0"])
+        y = E.conv(E.conv(y, pk["r1"]), pk["r4"])
         y = E.upsample(E.conv(y, pk["r8"]), 4, act=E.ACT_RELU)   # == relu(conv(4,1,1)(upsample(y))) of the reference
         y = E.conv(E.conv(y, pk["r10"]), pk["r12"])              # [B,1,H,W,1], ld 1
         E.logsumexp_sub(y.buf, B, y.H * y.W)
