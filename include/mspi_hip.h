@@ -379,6 +379,36 @@ int mspi_postprocess_u8(const float* logmap, unsigned char* out, void* workspace
                         int32_t Ho, int32_t Wo, mspi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Grey JPEG encoding on the device (csrc/jpegenc.hip).  Replaces: cv2.imwrite of the uint8 map (inference.py:89-91).
+ * Baseline sequential JPEG, one 8-bit component, 8x8 blocks in raster order, no restart markers, the Annex K luminance
+ * Huffman tables: libjpeg's file byte for byte (integer "islow" FDCT, its quantiser rounding, jpeg_quality_scaling), which
+ * is what PIL.Image.save(format="JPEG", quality=q) and cv2.imwrite write for a grey image. */
+typedef struct MspiJpegDesc {
+  int32_t B, H, W;              /* B maps [H, W] uint8; H, W in 1...65535 */
+  int32_t quality;              /* 1...100 */
+  int64_t pitch, map_stride;    /* bytes between rows / between maps; rows need no alignment */
+  int64_t file_stride, cap;     /* files row b starts at b * file_stride; nothing is written at or beyond cap of a row */
+  uint16_t div[64];             /* quantiser divisors 8 * q[k] in zigzag order: 8 * the DQT payload of the header */
+  const void* header;           /* DEVICE copy of what mspi_jpeg_gray_header wrote for (H, W, quality) */
+  int32_t header_len;
+} MspiJpegDesc;
+
+/* Host only (inference.py:89-91): SOI, APP0 (JFIF 1.01, units 0, density 1x1), DQT, SOF0, the DC and AC DHT segments and SOS
+ * into dst[0, cap): 328 bytes, the bytes libjpeg's writer puts in front of the scan.  Returns the length or MSPI_EINVAL. */
+int mspi_jpeg_gray_header(int32_t H, int32_t W, int32_t quality, unsigned char* dst, int64_t cap);
+/* Host only (inference.py:89-91): the worst-case file size of an H x W map -- 20 + 63 * 26 bits per block, every scan byte
+ * stuffed, header and EOI; 0 for H or W outside 1...65535. */
+size_t mspi_jpeg_gray_bound(int32_t H, int32_t W);
+/* Host only (inference.py:89-91): bytes of device workspace mspi_jpeg_gray_fwd needs (8-byte aligned); 0 for bad arguments. */
+size_t mspi_jpeg_gray_ws_bytes(int32_t B, int32_t H, int32_t W);
+/* Encode (inference.py:89-91): files[b * file_stride ...] = the JPEG file of maps[b], lengths[b] = its size in bytes.  Four
+ * launches on `stream`, integer arithmetic only, bitwise reproducible.  Refuses (MSPI_EINVAL) null pointers, H or W outside
+ * 1...65535, quality outside 1...100, divisors that are not the quality's, cap below mspi_jpeg_gray_bound(H, W) and maps
+ * whose bound does not fit the int32 length. */
+int mspi_jpeg_gray_fwd(const MspiJpegDesc* d, const unsigned char* maps, unsigned char* files, int32_t* lengths, void* ws,
+                       mspi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Fused channel MLP on rows:  y = res + W2 . act( W1 . LN(x) + b1 ) + b2,  the 4C-wide hidden
  * activation stays on the CU (csrc/mlp_fused.hip).  f16x3 split products, fp32 accumulate.
  * Replaces: timm ConvNeXt block norm -> mlp.fc1 -> GELU -> mlp.fc2 -> gamma -> + shortcut

@@ -106,6 +106,15 @@ class PermuteDesc(C.Structure):
     _fields_ = [("dims", C.c_int32 * 6), ("strides", C.c_int64 * 6), ("src_elems", C.c_int64)]
 
 
+class JpegDesc(C.Structure):
+    _fields_ = [
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("quality", C.c_int32),
+        ("pitch", C.c_int64), ("map_stride", C.c_int64), ("file_stride", C.c_int64), ("cap", C.c_int64),
+        ("div", C.c_uint16 * 64),
+        ("header", C.c_void_p), ("header_len", C.c_int32),
+    ]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -189,6 +198,10 @@ _SIGNATURES = {
     "mspi_mlp_variant": (C.c_int, [C.POINTER(MlpDesc)]),
     "mspi_postprocess_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mspi_postprocess_u8": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mspi_jpeg_gray_header": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64]),
+    "mspi_jpeg_gray_bound": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "mspi_jpeg_gray_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "mspi_jpeg_gray_fwd": (C.c_int, [C.POINTER(JpegDesc), _P, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1304,3 +1304,43 @@ def postprocess_u8(logmap, out_hw, out=None):
     check(lib.mspi_postprocess_u8(logmap.data_ptr(), out.data_ptr(), ws.data_ptr(), N, H, W, Ho, Wo, _stream()),
           "mspi_postprocess_u8")
     return out
+
+
+_JPEG_PLANS = {}
+
+
+def jpeg_encode_gray(maps_u8, quality=95):
+    """[B,H,W] uint8 grey maps (GPU) -> (files uint8 [B,cap], lengths int32 [B]), both on the GPU: files[b, :lengths[b]] is the
+    baseline JPEG file libjpeg writes for maps[b] at `quality` -- PIL.Image.save(format="JPEG", quality=quality), byte for
+    byte (inference.py:89-91 writes with cv2.imwrite).  Rows of `maps_u8` may be a view into a wider buffer (unit stride along
+    W).  The header template and the workspace are cached per (H, W, quality, B), so calls of one shape must be ordered on one
+    stream; no host synchronisation."""
+    lib = _lib.load()
+    _need_gpu(maps_u8)
+    if maps_u8.dtype != torch.uint8 or maps_u8.dim() != 3:
+        raise MspiError("jpeg_encode_gray: maps must be a uint8 [B,H,W] tensor, got %s %s" % (maps_u8.dtype, tuple(maps_u8.shape)))
+    B, H, W = maps_u8.shape
+    if maps_u8.stride(2) != 1 or maps_u8.stride(1) < W or (B > 1 and maps_u8.stride(0) < maps_u8.stride(1) * (H - 1) + W):
+        maps_u8 = maps_u8.contiguous()
+    key = (H, W, int(quality), B, maps_u8.device)
+    plan = _JPEG_PLANS.get(key)
+    if plan is None:
+        cap = lib.mspi_jpeg_gray_bound(H, W)
+        host = (C.c_ubyte * 512)()
+        n = lib.mspi_jpeg_gray_header(H, W, int(quality), host, 512)
+        check(min(n, 0), "mspi_jpeg_gray_header")
+        d = _lib.JpegDesc()
+        d.B, d.H, d.W, d.quality, d.file_stride, d.cap, d.header_len = B, H, W, int(quality), cap, cap, n
+        for k in range(64):
+            d.div[k] = 8 * host[25 + k]                  # the DQT payload: SOI 2 + APP0 18 + DQT marker, length, index 5
+        header = torch.tensor(list(host[:n]), dtype=torch.uint8).to(maps_u8.device)
+        ws = torch.empty(lib.mspi_jpeg_gray_ws_bytes(B, H, W), dtype=torch.uint8, device=maps_u8.device)
+        d.header = header.data_ptr()
+        plan = _JPEG_PLANS[key] = (d, header, ws, cap)
+    d, header, ws, cap = plan
+    d.pitch, d.map_stride = maps_u8.stride(1), maps_u8.stride(0)
+    files = torch.empty(B, cap, dtype=torch.uint8, device=maps_u8.device)
+    lengths = torch.empty(B, dtype=torch.int32, device=maps_u8.device)
+    check(lib.mspi_jpeg_gray_fwd(C.byref(d), maps_u8.data_ptr(), files.data_ptr(), lengths.data_ptr(), ws.data_ptr(), _stream()),
+          "mspi_jpeg_gray_fwd")
+    return files, lengths

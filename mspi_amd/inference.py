@@ -13,6 +13,10 @@ flags, same output files `save_path/<video>/<frame name>`; what differs:
   * frames are decoded on the host (PIL) and resized + normalised on the GPU with PIL's own fixed-point bilinear
     resampling (`preproc.resize_normalize`, bit-exact to PIL.Image.resize);
   * videos are sharded over ranks when launched with torch.distributed.run (one process per GPU, no collective);
+  * `--device_jpeg` (or MSPI_DEVICE_JPEG=1) also encodes the maps on the GPU (`engine.jpeg_encode_gray`: libjpeg's baseline
+    grey file, byte for byte what PIL writes), so ~20 KB of file instead of 300 KB of pixels comes back per map and the host
+    only writes bytes; `--workers N` decodes the input frames ahead of the loop on N host threads.  Both are off by default
+    and neither changes a byte of any written file;
   * cv2 / torchaudio / torchvision are not required: PIL does the frame decode + resize (what torchvision's
     transforms do on PIL images), scipy reads the wav, and torchaudio's sinc resampler and Spectrogram are
     restated on torch -- PARITY UNPINNED for those host-side third-party pieces (SURVEY.md section 8c);
@@ -159,11 +163,21 @@ def process(model, frames, frame_idx, vname, img_size, audio_feature=None, args=
         pred = model(frames, audio_feature.to(device, non_blocking=True), **kw)[0]
     else:
         pred = model(frames, **kw)[0]
-    maps = E.postprocess_u8(pred, (img_size[1], img_size[0])).cpu().numpy()      # img_size is (W, H) as in cv2.resize
+    names = frame_idx if isinstance(frame_idx, (list, tuple)) else [frame_idx]
+    maps = E.postprocess_u8(pred, (img_size[1], img_size[0]))                    # img_size is (W, H) as in cv2.resize
+    on_dev = [k for k, n in enumerate(names) if _is_jpeg_name(n)] if _device_jpeg(args) else []
+    if on_dev:
+        sel = maps if len(on_dev) == len(names) else maps[on_dev]
+        files, lengths = E.jpeg_encode_gray(sel, quality=95)
+        lengths = lengths.cpu()              # the synchronisation the .cpu() of the maps performs on the host path
+    rest = [k for k in range(len(names)) if k not in on_dev]
+    host_maps = (maps if not on_dev else maps[rest]).cpu().numpy() if rest else None
     E.check_range(sync=False)                # range guard of the f16x3 GEMMs (the .cpu() above synchronised): raise, never write NaN-as-0 maps
     os.makedirs(os.path.join(args.save_path, vname), exist_ok=True)
-    names = frame_idx if isinstance(frame_idx, (list, tuple)) else [frame_idx]
-    _write_maps(maps, names, vname, args)
+    if on_dev:
+        _write_files(files, lengths, [names[k] for k in on_dev], vname, args)
+    if rest:
+        _write_maps(host_maps, [names[k] for k in rest], vname, args)
 
 
 def _write_maps(maps, names, vname, args):
@@ -172,6 +186,57 @@ def _write_maps(maps, names, vname, args):
         # quality=95 is cv2.imwrite's default IMWRITE_JPEG_QUALITY (the reference writes with cv2, inference.py:90); PIL's
         # own default of 75 would change every saved map and the metrics computed from the files
         Image.fromarray(m).save(os.path.join(args.save_path, vname, name), quality=95)
+
+
+def _device_jpeg(args):
+    return bool(getattr(args, "device_jpeg", os.environ.get("MSPI_DEVICE_JPEG") == "1"))
+
+
+def _is_jpeg_name(name):
+    return name.lower().endswith((".jpg", ".jpeg"))     # what PIL's save() maps to its JPEG writer; other names take the host path
+
+
+_PINNED = {}
+
+
+def _write_files(files, lengths, names, vname, args):
+    """files [B,cap] uint8 on the GPU, lengths [B] on the host: copy only the columns a file of this batch reaches into a pinned
+    buffer that is reused from batch to batch, and write each file's bytes as they are."""
+    n, m = files.shape[0], int(lengths.max())
+    buf = _PINNED.get("files")
+    if buf is None or buf.shape[0] < n or buf.shape[1] < files.shape[1]:
+        buf = _PINNED["files"] = torch.empty(max(n, 0 if buf is None else buf.shape[0]), files.shape[1], dtype=torch.uint8).pin_memory()
+    host = buf[:n, :m]
+    host.copy_(files[:, :m])
+    host = host.numpy()
+    for b, name in enumerate(names):
+        with open(os.path.join(args.save_path, vname, name), "wb") as f:
+            f.write(host[b, : int(lengths[b])].tobytes())
+
+
+class _FrameDecoder:
+    """`--workers N`: decode frames ahead of the clip loop on N host threads (PIL releases the GIL while it decodes).  At most
+    `ahead` frames are in flight; the upload and the resize stay with the caller, on the loop's stream, in frame order."""
+
+    def __init__(self, paths, workers, ahead):
+        from concurrent.futures import ThreadPoolExecutor
+        self.paths, self.ahead, self.next, self.pending = paths, max(1, ahead), 0, {}
+        self.pool = ThreadPoolExecutor(max_workers=workers)
+
+    def get(self, j):
+        hi = min(len(self.paths), j + 1 + self.ahead)
+        for k in range(max(self.next, j), hi):
+            self.pending[k] = self.pool.submit(_decode_rgb, self.paths[k])
+        self.next = max(self.next, hi)
+        fut = self.pending.pop(j, None)
+        for k in [k for k in self.pending if k < j]:        # frames the loop skipped: it asks in increasing order
+            self.pending.pop(k).cancel()
+        return fut.result() if fut is not None else _decode_rgb(self.paths[j])
+
+    def close(self):
+        for fut in self.pending.values():
+            fut.cancel()
+        self.pool.shutdown(wait=True)
 
 
 class _WindowRunner:
@@ -241,13 +306,19 @@ class _WindowRunner:
 
 def torch_transform(path):
     """Resize to the model resolution, scale to [0,1], ImageNet-normalise (inference.py:154-165)."""
+    rgb = _decode_rgb(path)                                            # decode on the host,
+    return _upload_transform(rgb), (rgb.shape[1], rgb.shape[0])        # resize + ToTensor + Normalize on the GPU
+
+
+def _decode_rgb(path):
     from PIL import Image
+    return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8).copy()
+
+
+def _upload_transform(rgb):
     from . import preproc
-    img = Image.open(path).convert("RGB")
-    sz = img.size
-    rgb = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).to(device, non_blocking=True)     # decode on the host,
-    t = preproc.resize_normalize(rgb, (_RESOLUTION[0], _RESOLUTION[1]), IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD)
-    return t, sz                                                       # resize + ToTensor + Normalize on the GPU
+    rgb = torch.from_numpy(rgb).to(device, non_blocking=True)
+    return preproc.resize_normalize(rgb, (_RESOLUTION[0], _RESOLUTION[1]), IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD)
 
 
 def _flush(model, batch, vname, img_size, args, feats=None, runner=None):
@@ -332,6 +403,10 @@ def _inference_dataset(model, args):
     list_data = list_data[rank::world]            # videos are independent units: shard, no collective
     print(list_data)
     bs = max(1, getattr(args, "batch", 1))
+    if _device_jpeg(args) and getattr(args, "graph", False):
+        raise ValueError("--device_jpeg cannot be combined with --graph: the graph path hands back fixed-shape uint8 maps "
+                         "through its pinned slots, not files")
+    workers = max(0, int(getattr(args, "workers", 0) or 0))
     runner = _WindowRunner(model, bs, (640, 480), args.use_sound) if getattr(args, "graph", False) else None
     for vname in list_data:
         print("Processing: " + vname)
@@ -347,10 +422,11 @@ def _inference_dataset(model, args):
         n_wave = 0 if wave is None else wave.numel()
         img_size = (640, 480)
         loaded = {}
+        decoder = _FrameDecoder(list_frames, workers, 2 * bs) if workers > 0 else None
 
         def load_frame(j):
             if j not in loaded:
-                loaded[j] = torch_transform(list_frames[j])[0]
+                loaded[j] = torch_transform(list_frames[j])[0] if decoder is None else _upload_transform(decoder.get(j))
             return loaded[j]
 
         cache = None
@@ -383,6 +459,8 @@ def _inference_dataset(model, args):
             out = runner.finish()
             if out is not None:
                 _write_maps(*out, args)
+        if decoder is not None:
+            decoder.close()
     torch.cuda.current_stream().synchronize()   # whichever stream the loop ended on (it moves to an idle hardware queue)
 
 
@@ -418,7 +496,12 @@ if __name__ == "__main__":
                         help="replay one hipGraph per batch of windows, two batches in flight, instead of launching eagerly")
     parser.add_argument("--no_frame_cache", dest="cache_frames", action="store_false",
                         help="re-encode all 16 frames of every window with the image encoder, as upstream does")
+    parser.add_argument("--device_jpeg", action="store_true", default=os.environ.get("MSPI_DEVICE_JPEG") == "1",
+                        help="encode the saliency maps to JPEG on the GPU (the same bytes PIL writes); not with --graph")
+    parser.add_argument("--workers", default=0, type=int, help="host threads that decode input frames ahead of the loop (0: in the loop)")
     args = parser.parse_args()
+    if args.device_jpeg and args.graph:
+        parser.error("--device_jpeg cannot be combined with --graph (the graph path returns fixed-shape uint8 maps)")
     print(args)
     os.makedirs(args.save_path, exist_ok=True)
     if not torch.cuda.is_available():
