@@ -409,6 +409,53 @@ int mspi_jpeg_gray_fwd(const MspiJpegDesc* d, const unsigned char* maps, unsigne
                        mspi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * JPEG frame decoding on the device (csrc/jpegdec.hip).  Replaces: Image.open(path).convert('RGB') of the input frames
+ * (inference.py:154-165).  Baseline sequential DCT (SOF0), 8 bit, one interleaved scan, no restart interval; one component
+ * (grey, replicated to RGB) or YCbCr with 4:4:4, 4:2:2 (h2v1) or 4:2:0 (h2v2) sampling; any 8-bit DQT, any DHT; chroma width
+ * >= 2.  The result is libjpeg-turbo's default decode pixel for pixel: integer "islow" IDCT, fancy up-sampling, its fixed-point
+ * colour conversion.  Everything else is refused by the host parser and decoded by the caller on the host. */
+typedef struct MspiJpegDecTables {   /* the tables of one image; B of them on the DEVICE for mspi_jpeg_dec_fwd */
+  int32_t scan_len;                  /* bytes of entropy-coded data, stuffed zero bytes included */
+  int32_t reserved;
+  uint16_t quant[3][64];             /* the quantiser of each component, natural (row-major) order */
+  uint8_t comp_dc[4], comp_ac[4];    /* Huffman table (0 / 1) of each component */
+  uint8_t counts[4][16];             /* DC 0, DC 1, AC 0, AC 1: the number of codes of length 1...16 */
+  uint8_t vals[4][256];              /* their symbols in code order */
+} MspiJpegDecTables;
+typedef struct MspiJpegDecInfo {
+  int32_t H, W, ncomp;               /* ncomp 1 or 3 */
+  int32_t hs, vs;                    /* sampling factors of the first component: 1x1, 2x1 or 2x2 (1x1 for ncomp 1) */
+  int32_t scan_off, scan_len;        /* the entropy-coded bytes are file[scan_off, scan_off + scan_len) */
+  int32_t reserved;
+  MspiJpegDecTables tables;
+} MspiJpegDecInfo;
+typedef struct MspiJpegDecDesc {
+  int32_t B, H, W, ncomp, hs, vs;    /* B images of one geometry */
+  int32_t S;                         /* bits per subsequence: a multiple of 32, >= 128, ceil(8 * scan_cap / S) <= 1024 */
+  int32_t reserved;
+  int64_t scan_stride, scan_cap;     /* image b's scan starts at scans + b * scan_stride; every scan_len <= scan_cap */
+  int64_t pitch, img_stride;         /* bytes between rows (>= 3 * W) and between images of rgb */
+} MspiJpegDecDesc;
+
+/* Host only (inference.py:154-165): walk the markers of file[0, n) and fill *info.  The scan ends at the first FF that is
+ * followed by neither 00 nor an RST marker.  Returns MSPI_EINVAL, with the reason in mspi_last_error(), for what the device
+ * does not decode: progressive, arithmetic coding, 12 bit, a restart interval, several scans, 4 components, an Adobe
+ * transform other than 1, other sampling factors, 16-bit DQT, missing tables, empty or truncated headers. */
+int mspi_jpeg_dec_parse(const unsigned char* file, int64_t n, MspiJpegDecInfo* info);
+/* Host only (inference.py:154-165): bytes of device workspace mspi_jpeg_dec_fwd needs (16-byte aligned); 0 for a descriptor
+ * it refuses. */
+size_t mspi_jpeg_dec_ws_bytes(const MspiJpegDecDesc* d);
+/* Decode (inference.py:154-165): rgb[b * img_stride + y * pitch + 3 * x + c] = the pixels of image b.  scans: the stuffed scan
+ * bytes on the device; tables: B MspiJpegDecTables on the device, 8-byte aligned; status[b] = 0 when the scan held exactly the
+ * expected blocks and ended inside its final byte (1 / 2: fewer / more blocks, 3: ended elsewhere; the pixels are then
+ * undefined but stay inside the image); passes[b] = passes of the entropy decoder behind the first (the guess), the confirming one
+ * included.  Launches on `stream` only (unstuff, entropy decode, DC prediction, IDCT, up-sample + convert, one memset), no
+ * allocation, no host synchronisation, integer arithmetic only: bitwise reproducible.  Refuses (MSPI_EINVAL) null pointers,
+ * bad sizes or sampling, pitch < 3 * W, a bad S and more than 1024 subsequences before any launch. */
+int mspi_jpeg_dec_fwd(const MspiJpegDecDesc* d, const unsigned char* scans, const MspiJpegDecTables* tables, unsigned char* rgb,
+                      int32_t* status, int32_t* passes, void* ws, mspi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Fused channel MLP on rows:  y = res + W2 . act( W1 . LN(x) + b1 ) + b2,  the 4C-wide hidden
  * activation stays on the CU (csrc/mlp_fused.hip).  f16x3 split products, fp32 accumulate.
  * Replaces: timm ConvNeXt block norm -> mlp.fc1 -> GELU -> mlp.fc2 -> gamma -> + shortcut

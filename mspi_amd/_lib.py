@@ -115,6 +115,32 @@ class JpegDesc(C.Structure):
     ]
 
 
+class JpegDecTables(C.Structure):
+    _fields_ = [
+        ("scan_len", C.c_int32), ("reserved", C.c_int32),
+        ("quant", (C.c_uint16 * 64) * 3),
+        ("comp_dc", C.c_uint8 * 4), ("comp_ac", C.c_uint8 * 4),
+        ("counts", (C.c_uint8 * 16) * 4),
+        ("vals", (C.c_uint8 * 256) * 4),
+    ]
+
+
+class JpegDecInfo(C.Structure):
+    _fields_ = [
+        ("H", C.c_int32), ("W", C.c_int32), ("ncomp", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+        ("scan_off", C.c_int32), ("scan_len", C.c_int32), ("reserved", C.c_int32),
+        ("tables", JpegDecTables),
+    ]
+
+
+class JpegDecDesc(C.Structure):
+    _fields_ = [
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("ncomp", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+        ("S", C.c_int32), ("reserved", C.c_int32),
+        ("scan_stride", C.c_int64), ("scan_cap", C.c_int64), ("pitch", C.c_int64), ("img_stride", C.c_int64),
+    ]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -202,6 +228,9 @@ _SIGNATURES = {
     "mspi_jpeg_gray_bound": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mspi_jpeg_gray_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "mspi_jpeg_gray_fwd": (C.c_int, [C.POINTER(JpegDesc), _P, _P, _P, _P, _P]),
+    "mspi_jpeg_dec_parse": (C.c_int, [_P, C.c_int64, C.POINTER(JpegDecInfo)]),
+    "mspi_jpeg_dec_ws_bytes": (C.c_size_t, [C.POINTER(JpegDecDesc)]),
+    "mspi_jpeg_dec_fwd": (C.c_int, [C.POINTER(JpegDecDesc), _P, _P, _P, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -5,7 +5,9 @@ video_audio/), same clip list.  What differs: iterating it yields BATCHES THAT A
 a DataLoader to collate --
 
   * frames img_%05d.jpg are decoded with PIL on a small pool of host threads (one batch ahead of the consumer), uploaded as
-    uint8, grouped by source size and written into the [B,3,T,H,W] clip tensor by one `preproc.assemble_clips` launch per
+    uint8 -- or, with device_decode=True, only read by the pool and decoded on the device (`preproc.decode_frames`, the same
+    pixels; files the device does not take fall back to PIL) --, grouped by source size and written into the [B,3,T,H,W]
+    clip tensor by one `preproc.assemble_clips` launch per
     size group (PIL's resize + ToTensor + Normalize, bit for bit);
   * the label eyeMap_%05d.jpg is resized on the device (`evaluate.resize_maps`, cv2.resize upstream) and divided by 255
     where its maximum exceeds 1 (:176-182);
@@ -42,6 +44,14 @@ def load_rgb(path):
         return np.array(im.convert("RGB"), dtype=np.uint8)
 
 
+def read_frame(path):
+    """The bytes of a frame file (device_decode: the frame is decoded on the device)."""
+    if not os.path.exists(path):
+        raise FileNotFoundError("avsp_dataloader: missing frame %s" % path)
+    with open(path, "rb") as f:
+        return f.read()
+
+
 def _gray(path):
     if not os.path.exists(path):
         raise FileNotFoundError("avsp_dataloader: missing annotation %s" % path)
@@ -60,13 +70,14 @@ def _fixation(root, no):
 
 class AudioVisualDataset:
     def __init__(self, data_root, dataset_name="DIEM", split=1, len_clip=32, mode="train", use_sound=True, size=(224, 224),
-                 batch_size=8, with_fixations=False, generator=None, workers=8, device=None):
+                 batch_size=8, with_fixations=False, generator=None, workers=8, device=None, device_decode=False):
         if mode not in ("train", "val", "test"):
             raise MspiError("avsp_dataloader: mode must be train, val or test, got %r" % (mode,))
         self.path_data, self.dataset_name, self.mode = data_root, dataset_name, mode
         self.use_sound, self.len_snippet, self.size = use_sound, int(len_clip), (int(size[0]), int(size[1]))
         self.batch_size, self.with_fixations = max(1, int(batch_size)), with_fixations
         self.generator, self.workers, self.device = generator, max(1, int(workers)), device
+        self.device_decode = bool(device_decode)
         if dataset_name == "DIEM":
             file_name = "DIEM_list_{}_fps.txt".format(mode)
         else:
@@ -125,7 +136,8 @@ class AudioVisualDataset:
         frames, labels, fixes = [], [], []
         for v, start in items:
             clip_dir = os.path.join(self.path_data, "video_frames", self.dataset_name, v)
-            frames += [pool.submit(load_rgb, os.path.join(clip_dir, "img_%05d.jpg" % (start + i + 1))) for i in range(T)]
+            frames += [pool.submit(read_frame if self.device_decode else load_rgb,
+                                   os.path.join(clip_dir, "img_%05d.jpg" % (start + i + 1))) for i in range(T)]
             labels.append(pool.submit(_gray, os.path.join(self._maps(v), "eyeMap_%05d.jpg" % (start + T))))
             if self.with_fixations:
                 fixes.append(pool.submit(_fixation, os.path.join(self.path_data, "annotations", self.dataset_name, v), start + T))
@@ -138,6 +150,15 @@ class AudioVisualDataset:
         for i, a in enumerate(arrays):
             groups.setdefault(a.shape, []).append(i)
         return [(idx, torch.from_numpy(np.stack([arrays[i] for i in idx])).to(device)) for idx in groups.values()]
+
+    def _frames_by_shape(self, frames, device):
+        """_by_shape of the batch's frames; with device_decode they arrive as file bytes and are decoded on the device."""
+        if not self.device_decode:
+            return self._by_shape(frames, device)
+        groups = {}
+        for i, t in enumerate(preproc.decode_frames(frames, device)):
+            groups.setdefault(tuple(t.shape), []).append((i, t))
+        return [([i for i, _ in g], torch.stack([t for _, t in g])) for g in groups.values()]
 
     def _wave(self, video, device):
         if video not in self._waves:
@@ -169,7 +190,7 @@ class AudioVisualDataset:
         frames = [f.result() for f in frames]
         B, T = len(items), self.len_snippet
         clips = torch.empty(B, 3, T, self.size[0], self.size[1], dtype=torch.float32, device=device)
-        for idx, dev_frames in self._by_shape(frames, device):
+        for idx, dev_frames in self._frames_by_shape(frames, device):
             preproc.assemble_clips(dev_frames, idx, clips, IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD)
         label = torch.empty(B, self.size[0], self.size[1], dtype=torch.float32, device=device)
         for idx, maps in self._by_shape([f.result() for f in labels], device):

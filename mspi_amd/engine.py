@@ -11,6 +11,7 @@
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1344,3 +1345,89 @@ def jpeg_encode_gray(maps_u8, quality=95):
     check(lib.mspi_jpeg_gray_fwd(C.byref(d), maps_u8.data_ptr(), files.data_ptr(), lengths.data_ptr(), ws.data_ptr(), _stream()),
           "mspi_jpeg_gray_fwd")
     return files, lengths
+
+
+# ----------------------------------------------------------------------------- JPEG frame decoding (csrc/jpegdec.hip)
+_JPEG_DEC = {}      # per device: pinned staging buffer + the event of its last upload, device input buffer, workspace
+
+
+def jpeg_probe(data):
+    """The parsed header (a _lib.JpegDecInfo: H, W, ncomp, hs, vs, scan_off, scan_len, tables) of a JPEG file given as bytes,
+    or None where the device decoder does not take it (progressive, restart markers, CMYK, ...: `_lib.load().mspi_last_error()`
+    says which) -- the caller then decodes that file on the host.  Host only."""
+    lib = _lib.load()
+    info = _lib.JpegDecInfo()
+    if lib.mspi_jpeg_dec_parse(C.cast(C.c_char_p(bytes(data)), C.c_void_p), len(data), C.byref(info)) != 0:
+        return None
+    return info
+
+
+def jpeg_subseq_bits(scan_bytes):
+    """Bits per subsequence for scans of up to `scan_bytes` bytes: at most 1024 subsequences, none shorter than 1024 bits."""
+    return max(1024, (-(-8 * scan_bytes // 1024) + 31) // 32 * 32)
+
+
+def _grown(slot, key, nbytes, make):
+    buf = slot.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = slot[key] = make(max(nbytes, 0 if buf is None else 2 * buf.numel()))
+    return buf
+
+
+def jpeg_decode_rgb(files, subseq_bits=None, device=None, infos=None):
+    """files: a list of N `bytes`, baseline JPEG files of ONE geometry (size, components, sampling) -> (rgb uint8 [N,H,W,3],
+    status int32 [N], passes int32 [N]), all on the GPU: rgb[i] is np.asarray(PIL.Image.open(files[i]).convert("RGB")) pixel
+    for pixel wherever status[i] == 0 (inference.py:154-165 decodes with PIL); a non-zero status marks a truncated or corrupt
+    scan, whose pixels the caller replaces.  Only the scans and tables are uploaded: they are packed into one pinned staging
+    buffer that is reused from call to call (the call waits for the previous upload from it) and go up in one copy on the
+    current stream; the staging, input and workspace buffers are cached per device, so calls must be ordered on one stream.
+    Raises MspiError for mixed geometry and for a file the parser refuses (`jpeg_probe` tells in advance)."""
+    lib = _lib.load()
+    if not files:
+        raise MspiError("jpeg_decode_rgb: no files")
+    if infos is None:
+        infos = [jpeg_probe(f) for f in files]
+    for k, info in enumerate(infos):
+        if info is None:
+            jpeg_probe(files[k])
+            raise MspiError("jpeg_decode_rgb: file %d: %s" % (k, lib.mspi_last_error().decode("utf-8", "replace")))
+    geo = lambda i: (i.H, i.W, i.ncomp, i.hs, i.vs)      # noqa: E731
+    if any(geo(i) != geo(infos[0]) for i in infos):
+        raise MspiError("jpeg_decode_rgb: mixed geometry in one batch: %s" % sorted({geo(i) for i in infos}))
+    if device is None and not torch.cuda.is_available():
+        raise MspiError("jpeg_decode_rgb: needs an MI355X; there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise MspiError("jpeg_decode_rgb: runs on the GPU only (device %s)" % dev)
+    N, first = len(files), infos[0]
+    cap = (max(i.scan_len for i in infos) + 15) // 16 * 16
+    tsz = C.sizeof(_lib.JpegDecTables)
+    total = N * (tsz + cap)
+    d = _lib.JpegDecDesc()
+    d.B, d.H, d.W, d.ncomp, d.hs, d.vs = N, first.H, first.W, first.ncomp, first.hs, first.vs
+    d.S = int(subseq_bits) if subseq_bits is not None else jpeg_subseq_bits(cap)
+    d.scan_stride, d.scan_cap, d.pitch, d.img_stride = cap, cap, 3 * first.W, 3 * first.W * first.H
+    need = lib.mspi_jpeg_dec_ws_bytes(C.byref(d))
+    if need == 0:
+        raise MspiError("jpeg_decode_rgb: %s" % lib.mspi_last_error().decode("utf-8", "replace"))
+    slot = _JPEG_DEC.setdefault(dev, {})
+    stage = _grown(slot, "stage", total, lambda n: torch.empty(n, dtype=torch.uint8).pin_memory())
+    if slot.get("uploaded") is not None:
+        slot["uploaded"].synchronize()               # the previous call's copy out of the staging buffer
+    host = stage.numpy()
+    for k, (f, info) in enumerate(zip(files, infos)):
+        host[k * tsz:(k + 1) * tsz] = np.frombuffer(C.string_at(C.addressof(info.tables), tsz), dtype=np.uint8)
+        host[N * tsz + k * cap:N * tsz + k * cap + info.scan_len] = np.frombuffer(f, dtype=np.uint8, count=info.scan_len,
+                                                                                  offset=info.scan_off)
+    inp = _grown(slot, "input", total, lambda n: torch.empty(n, dtype=torch.uint8, device=dev))
+    ws = _grown(slot, "ws", need, lambda n: torch.empty(n, dtype=torch.uint8, device=dev))
+    with torch.cuda.device(dev):
+        inp[:total].copy_(stage[:total], non_blocking=True)
+        slot["uploaded"] = torch.cuda.Event()
+        slot["uploaded"].record()
+        rgb = torch.empty(N, first.H, first.W, 3, dtype=torch.uint8, device=dev)
+        status = torch.empty(N, dtype=torch.int32, device=dev)
+        passes = torch.empty(N, dtype=torch.int32, device=dev)
+        check(lib.mspi_jpeg_dec_fwd(C.byref(d), inp.data_ptr() + N * tsz, inp.data_ptr(), rgb.data_ptr(), status.data_ptr(),
+                                    passes.data_ptr(), ws.data_ptr(), _stream()), "mspi_jpeg_dec_fwd")
+    return rgb, status, passes

@@ -17,6 +17,11 @@ flags, same output files `save_path/<video>/<frame name>`; what differs:
     grey file, byte for byte what PIL writes), so ~20 KB of file instead of 300 KB of pixels comes back per map and the host
     only writes bytes; `--workers N` decodes the input frames ahead of the loop on N host threads.  Both are off by default
     and neither changes a byte of any written file;
+  * `--device_decode` (or MSPI_DEVICE_DECODE=1) decodes the input frames on the GPU too (`engine.jpeg_decode_rgb`: libjpeg-turbo's
+    baseline decode, pixel for pixel what PIL hands back), so the loop's thread only reads file bytes (on the `--workers`
+    pool when there is one) and ~90 KB of file instead of 900 KB of pixels goes up per frame; files the device does not take
+    (progressive, restart markers, CMYK, a damaged scan) are decoded with PIL as before.  Off by default; combines with
+    `--device_jpeg`, `--workers` and `--graph`;
   * cv2 / torchaudio / torchvision are not required: PIL does the frame decode + resize (what torchvision's
     transforms do on PIL images), scipy reads the wav, and torchaudio's sinc resampler and Spectrogram are
     restated on torch -- PARITY UNPINNED for those host-side third-party pieces (SURVEY.md section 8c);
@@ -239,6 +244,52 @@ class _FrameDecoder:
         self.pool.shutdown(wait=True)
 
 
+def _device_decode(args):
+    return bool(getattr(args, "device_decode", os.environ.get("MSPI_DEVICE_DECODE") == "1"))
+
+
+def _read_bytes(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
+class _DeviceFrameDecoder:
+    """`--device_decode`: frames are decoded on the GPU, `chunk` of them ahead of the loop per launch sequence
+    (`preproc.decode_frames`, on the loop's stream); `get(j)` hands back a uint8 [H,W,3] device tensor.  The file bytes are
+    read in the loop, or with `workers` > 0 on a pool that reads one chunk ahead.  Frames the parser refuses or whose scan the
+    device reports as damaged go through `_decode_rgb`."""
+
+    def __init__(self, paths, workers, chunk):
+        from concurrent.futures import ThreadPoolExecutor
+        self.paths, self.chunk, self.ready, self.pending, self.stats = paths, max(1, chunk), {}, {}, {}
+        self.pool = ThreadPoolExecutor(max_workers=workers) if workers > 0 else None
+
+    def _blob(self, k):
+        fut = self.pending.pop(k, None)
+        return fut.result() if fut is not None else _read_bytes(self.paths[k])
+
+    def get(self, j):
+        if j not in self.ready:                             # the loop asks in increasing order: earlier frames are done with
+            from . import preproc
+            hi = min(len(self.paths), j + self.chunk)
+            if self.pool is not None:
+                for k in range(j, min(len(self.paths), hi + self.chunk)):
+                    if k not in self.pending:
+                        self.pending[k] = self.pool.submit(_read_bytes, self.paths[k])
+                for k in [k for k in self.pending if k < j]:
+                    self.pending.pop(k).cancel()
+            blobs = [self._blob(k) for k in range(j, hi)]
+            frames = preproc.decode_frames(blobs, device, self.stats, host_decode=lambda k: _decode_rgb(self.paths[j + k]))
+            self.ready = dict(zip(range(j, hi), frames))
+        return self.ready[j]
+
+    def close(self):
+        for fut in self.pending.values():
+            fut.cancel()
+        if self.pool is not None:
+            self.pool.shutdown(wait=True)
+
+
 class _WindowRunner:
     """The clip loop's launch path: model forward + post-processing of a batch of `bs` windows as one hipGraph per input
     shape (frames are all resized to one resolution, so a run captures once), two batches in flight.  `run()` queues a
@@ -317,7 +368,8 @@ def _decode_rgb(path):
 
 def _upload_transform(rgb):
     from . import preproc
-    rgb = torch.from_numpy(rgb).to(device, non_blocking=True)
+    if not torch.is_tensor(rgb):                 # a frame decoded on the device is there already
+        rgb = torch.from_numpy(rgb).to(device, non_blocking=True)
     return preproc.resize_normalize(rgb, (_RESOLUTION[0], _RESOLUTION[1]), IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD)
 
 
@@ -422,7 +474,10 @@ def _inference_dataset(model, args):
         n_wave = 0 if wave is None else wave.numel()
         img_size = (640, 480)
         loaded = {}
-        decoder = _FrameDecoder(list_frames, workers, 2 * bs) if workers > 0 else None
+        if _device_decode(args):
+            decoder = _DeviceFrameDecoder(list_frames, workers, 2 * bs)
+        else:
+            decoder = _FrameDecoder(list_frames, workers, 2 * bs) if workers > 0 else None
 
         def load_frame(j):
             if j not in loaded:
@@ -499,6 +554,8 @@ if __name__ == "__main__":
     parser.add_argument("--device_jpeg", action="store_true", default=os.environ.get("MSPI_DEVICE_JPEG") == "1",
                         help="encode the saliency maps to JPEG on the GPU (the same bytes PIL writes); not with --graph")
     parser.add_argument("--workers", default=0, type=int, help="host threads that decode input frames ahead of the loop (0: in the loop)")
+    parser.add_argument("--device_decode", action="store_true", default=os.environ.get("MSPI_DEVICE_DECODE") == "1",
+                        help="decode the input JPEG frames on the GPU (the same pixels PIL decodes); --workers then only read the files")
     args = parser.parse_args()
     if args.device_jpeg and args.graph:
         parser.error("--device_jpeg cannot be combined with --graph (the graph path returns fixed-shape uint8 maps)")

@@ -155,3 +155,41 @@ def assemble_clips(frames_u8, slots, out, mean, std, slots_dev=None):
                                         vk.data_ptr(), vks, m, s, torch.cuda.current_stream().cuda_stream),
           "mspi_clip_resize_norm_fwd")
     return out
+
+
+def decode_rgb_bytes(data):
+    """uint8 [H,W,3]: the frame as upstream reads it (PIL, convert('RGB'), inference.py:154-165), from the file's bytes."""
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        return np.array(im.convert("RGB"), dtype=np.uint8)
+
+
+def decode_frames(blobs, device, stats=None, host_decode=None):
+    """Input frames given as the bytes of their JPEG files -> a list of uint8 [H,W,3] tensors on `device`, what PIL decodes
+    pixel for pixel.  Files the device decoder takes (`engine.jpeg_probe`) are grouped by geometry and decoded by one
+    `engine.jpeg_decode_rgb` launch sequence per group on the current stream; only their bytes are uploaded.  A file the
+    parser refuses (progressive, restart markers, CMYK, ...) and a file whose scan the device reports as truncated or corrupt
+    (status != 0) are decoded with PIL on the host and uploaded as pixels.  Reading the status words synchronises the stream
+    once per call.  stats: a dict whose "device" / "host" counters are advanced; host_decode(k): the caller's own host decode
+    of frame k (default: PIL on blobs[k])."""
+    from . import engine as E
+    out, groups, infos = [None] * len(blobs), {}, [E.jpeg_probe(b) for b in blobs]
+    for k, info in enumerate(infos):
+        if info is not None:
+            groups.setdefault((info.H, info.W, info.ncomp, info.hs, info.vs), []).append(k)
+    done = []
+    for idx in groups.values():
+        rgb, status, _ = E.jpeg_decode_rgb([blobs[k] for k in idx], device=device, infos=[infos[k] for k in idx])
+        done.append((idx, rgb, status))
+    for idx, rgb, status in done:
+        for j, (k, bad) in enumerate(zip(idx, status.tolist())):
+            if not bad:
+                out[k] = rgb[j]
+    host = [k for k in range(len(blobs)) if out[k] is None]
+    for k in host:
+        out[k] = torch.from_numpy(decode_rgb_bytes(blobs[k]) if host_decode is None else host_decode(k)).to(device, non_blocking=True)
+    if stats is not None:
+        stats["device"] = stats.get("device", 0) + len(blobs) - len(host)
+        stats["host"] = stats.get("host", 0) + len(host)
+    return out

@@ -2,7 +2,7 @@
 (avsp_dataloader.py:83-193, engine_train.py:84-125) on the MI355X.
 
     python -m mspi_amd.validate --weight w.pt --path_data ./AuViDataset --dataset AVAD --split 2 --mode test --model x3dl
-        [--resolution H W] [--clip_size 16] [--batch 8] [--no_sound] [--fixations] [--workers 8] [--json OUT]
+        [--resolution H W] [--clip_size 16] [--batch 8] [--no_sound] [--fixations] [--workers 8] [--device_decode] [--json OUT]
 
 inference.build_model builds the model, avsp_dataloader.AudioVisualDataset yields device batches (frames decoded on the
 host, clips assembled by one launch per batch) and metrics.validation_one_epoch scores them.  Prints upstream's line
@@ -42,7 +42,7 @@ def format_line(stats):
 
 @torch.no_grad()
 def validate(model, data_root, dataset="AVAD", split=2, mode="val", resolution=(224, 384), clip_size=16, batch=8, use_sound=True,
-             fixations=False, workers=8, device=None, generator=None):
+             fixations=False, workers=8, device=None, generator=None, device_decode=False):
     """{"loss", "kld", "cc", "sim"[, "nss", "auc_j"]} of `model` (on the device, eval) over the clips of the split, as
     metrics.validation_one_epoch computes them from the batches of avsp_dataloader.AudioVisualDataset.  fixations: also
     NSS / AUC-Judd against the fixation maps.  The f16x3 range guard is read once at the end and raises."""
@@ -52,7 +52,8 @@ def validate(model, data_root, dataset="AVAD", split=2, mode="val", resolution=(
     _single_rank()
     device = _cuda(device)
     data = AudioVisualDataset(data_root, dataset, split, clip_size, mode, use_sound, tuple(resolution), batch_size=batch,
-                              with_fixations=fixations, generator=generator, workers=workers, device=device)
+                              with_fixations=fixations, generator=generator, workers=workers, device=device,
+                              device_decode=device_decode)
     cfg = types.SimpleNamespace(DATA=types.SimpleNamespace(USE_SOUND=bool(use_sound)))
     stats = M.validation_one_epoch(model, data, device, cfg)
     E.check_range(sync=True)                 # raise rather than report numbers computed from inf / NaN activations
@@ -73,6 +74,8 @@ def build_parser():
     parser.add_argument("--no_sound", dest="use_sound", action="store_false", help="the visual-only model")
     parser.add_argument("--fixations", action="store_true", help="also NSS / AUC-Judd against the fixation maps")
     parser.add_argument("--workers", default=8, type=int, help="host threads decoding JPEGs")
+    parser.add_argument("--device_decode", action="store_true", default=os.environ.get("MSPI_DEVICE_DECODE") == "1",
+                        help="decode the frames on the GPU (the same pixels); the host threads then only read the files")
     parser.add_argument("--json", default=None, type=str, help="also write the result dict to this file")
     return parser
 
@@ -90,7 +93,7 @@ def main(argv=None):
     I._RESOLUTION[:] = args.resolution
     model = I.build_model(args.model, args.resolution, weight=args.weight, use_sound=args.use_sound)
     stats = validate(model, args.path_data, args.dataset, args.split, args.mode, args.resolution, args.clip_size, args.batch,
-                     args.use_sound, args.fixations, args.workers, device)
+                     args.use_sound, args.fixations, args.workers, device, device_decode=args.device_decode)
     print(format_line(stats))
     print(json.dumps(stats))
     if args.json:
