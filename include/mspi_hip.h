@@ -50,7 +50,7 @@ enum { MSPI_PREC_F32 = 0, MSPI_PREC_F16X3 = 1 };
 int mspi_version(void);
 const char* mspi_last_error(void);
 /* Range guard.  f16x3 operands must satisfy |x| < 65504 (beyond it the f16 hi half is inf).  The GEMM kernels (mspi_conv_fwd,
- * mspi_conv_splitk_fwd, mspi_gemm_sp_fwd, mspi_rowgemm_fwd, mspi_mlp_fwd, mspi_x3d_ab_fwd) check their pre-activation
+ * mspi_conv_splitk_fwd, mspi_gemm_sp_fwd, mspi_rowgemm_fwd, mspi_mlp_fwd, mspi_x3d_ab_fwd, mspi_x3d_ab_s2_fwd) check their pre-activation
  * results and store 1 into *word when one is inf or NaN -- whatever the cause (operand out of range, non-finite input).
  * `word` must be device-visible: a 4-byte word of pinned host memory (hipHostMalloc / torch pin_memory) lets the caller read
  * it without a device call, after the event that covers the launches; the caller clears it.  NULL (default): no report.
@@ -316,6 +316,52 @@ int mspi_x3d_ab_fwd(const MspiX3dAbDesc* d, const void* x, const void* wa_packed
  * KS * 10000 + TH * 1000 + TW * 10 + SL (KS = ceil(Cin / 32), 7 x 14 tiles when W % 14 == 0, else 7 x 7); -1 = a
  * descriptor the launch refuses.  mspi_x3d_ab_fwd selects by this function. */
 int mspi_x3d_ab_variant(const MspiX3dAbDesc* d);
+
+/* ------------------------------------------------------------------------------------
+ * The same first half for the FIRST block of a stage, whose `b` has spatial stride 2 (csrc/x3d_head.hip):
+ *   u = act( b_bn( dw3x3x3, stride (1,2,2), pad (1,1,1) ( relu( a_bn( a(x) ) ) ) ) )
+ * The `a` output, four times the size of u, stays in LDS instead of being written and read back at the input resolution.
+ * x: [N,T,H,W] rows of ldx floats; u: [N,T,H/2,W/2] rows of ldu floats.  wa_packed, wb, bias_a, bias_b, act, wa_scale and
+ * pool ([N][mspi_x3d_ab_s2_pool_rows(d)][Cmid], one row per workgroup, pad channels zero, consumed by mspi_se_gate) are
+ * those of mspi_x3d_ab_fwd; mspi_x3d_ab_packed_bytes(Cin, Cmid) gives the size of wa_packed.
+ * H and W even, (H/2) % 7 == 0 and (W/2) % 7 == 0 (7 x 7 output tiles, so W/2 % 14 == 0 is covered); Cin <= 96, Cin % 8 == 0,
+ * Cmid % 4 == 0; one frame of x below 2^31 floats. */
+typedef struct MspiX3dAbS2Desc {
+  int32_t N, T, H, W;              /* the INPUT extent */
+  int32_t Cin, Cmid;               /* stored channel counts */
+  int64_t ldx, ldu;
+  int32_t act;                     /* MSPI_ACT_NONE or MSPI_ACT_SWISH, applied to u (not to the pooled sums) */
+  float wa_scale;                  /* power-of-two pre-scale of a's weights */
+} MspiX3dAbS2Desc;
+
+int mspi_x3d_ab_s2_supported(const MspiX3dAbS2Desc* d);
+int mspi_x3d_ab_s2_pool_rows(const MspiX3dAbS2Desc* d);   /* tiles * T segments, tiles = (H/14) * (W/14) */
+int mspi_x3d_ab_s2_fwd(const MspiX3dAbS2Desc* d, const void* x, const void* wa_packed, const void* bias_a, const void* wb,
+                       const void* bias_b, void* u, void* pool /*or NULL*/, mspi_stream_t stream);
+/* Which instantiation mspi_x3d_ab_s2_fwd launches (host only): x3d_ab_s2_kernel<KS> as KS * 10000 + 7071 (KS = ceil(Cin /
+ * 32), 7 x 7 output tiles, one output per thread); -1 = a descriptor the launch refuses. */
+int mspi_x3d_ab_s2_variant(const MspiX3dAbS2Desc* d);
+
+/* ------------------------------------------------------------------------------------
+ * X3D stem in one launch (csrc/x3d_head.hip; SlowFast/stem_helper.py:207-290):
+ *   y = relu( bn( conv (5,1,1) pad 2, depthwise ( conv_xy (1,3,3), stride (1,2,2), pad (0,1,1), 3 -> 24, no bias ) ) )
+ * x: the raw clip [N,3,T,H,W], fp32, element strides sN, sC, sT, sH, sW (non-negative; (H-1)*sH + (W-1)*sW < 2^31).
+ * y: [N,T,Ho,Wo] rows of ldy floats, 24 channels, Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1.  wxy: fp32 [27][24], tap (ci,kh,kw)
+ * major; wt: fp32 [5][24] temporal taps with the BN scale folded; bias: the folded BN shift [24] -- all three are HOST
+ * pointers: the 792 weights travel as kernel arguments (read into SGPRs), and are copied at the call, so a captured graph
+ * holds its own copy.  All products are fp32 FMAs (no f16 split: no operand range to watch).  The conv_xy result stays in
+ * registers. */
+typedef struct MspiX3dStemDesc {
+  int32_t N, T, H, W;
+  int64_t sN, sC, sT, sH, sW;
+  int64_t ldy;
+} MspiX3dStemDesc;
+
+int mspi_x3d_stem_supported(const MspiX3dStemDesc* d);
+/* x3d_stem_kernel has one instantiation; the code is the number of frames per T segment of the launch; -1 = refused. */
+int mspi_x3d_stem_variant(const MspiX3dStemDesc* d);
+int mspi_x3d_stem_fwd(const MspiX3dStemDesc* d, const void* x, const void* wxy, const void* wt, const void* bias, void* y,
+                      mspi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Max pooling, channels-last, -inf padding.

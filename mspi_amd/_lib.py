@@ -102,6 +102,18 @@ class X3dAbDesc(C.Structure):
     ]
 
 
+class X3dAbS2Desc(C.Structure):
+    _fields_ = list(X3dAbDesc._fields_)     # same members, the extent is the input's (include/mspi_hip.h, MspiX3dAbS2Desc)
+
+
+class X3dStemDesc(C.Structure):
+    _fields_ = [
+        ("N", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("sN", C.c_int64), ("sC", C.c_int64), ("sT", C.c_int64), ("sH", C.c_int64), ("sW", C.c_int64),
+        ("ldy", C.c_int64),
+    ]
+
+
 class PermuteDesc(C.Structure):
     _fields_ = [("dims", C.c_int32 * 6), ("strides", C.c_int64 * 6), ("src_elems", C.c_int64)]
 
@@ -219,6 +231,13 @@ _SIGNATURES = {
     "mspi_x3d_ab_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mspi_x3d_ab_fwd": (C.c_int, [C.POINTER(X3dAbDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "mspi_x3d_ab_variant": (C.c_int, [C.POINTER(X3dAbDesc)]),
+    "mspi_x3d_ab_s2_supported": (C.c_int, [C.POINTER(X3dAbS2Desc)]),
+    "mspi_x3d_ab_s2_pool_rows": (C.c_int, [C.POINTER(X3dAbS2Desc)]),
+    "mspi_x3d_ab_s2_fwd": (C.c_int, [C.POINTER(X3dAbS2Desc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mspi_x3d_ab_s2_variant": (C.c_int, [C.POINTER(X3dAbS2Desc)]),
+    "mspi_x3d_stem_supported": (C.c_int, [C.POINTER(X3dStemDesc)]),
+    "mspi_x3d_stem_variant": (C.c_int, [C.POINTER(X3dStemDesc)]),
+    "mspi_x3d_stem_fwd": (C.c_int, [C.POINTER(X3dStemDesc), _P, _P, _P, _P, _P, _P]),
     "mspi_mlp_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mspi_mlp_fwd": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mspi_mlp_variant": (C.c_int, [C.POINTER(MlpDesc)]),

@@ -17,6 +17,11 @@ from .. import engine as E
 from ..module import HipModule
 
 
+# X3D stem as one launch (csrc/x3d_head.hip, mspi_x3d_stem_fwd) instead of conv_xy + temporal depthwise conv:
+# MSPI_X3D_STEM_FUSED = 1 (default) | 0 (A/B)
+STEM_FUSED = os.environ.get("MSPI_X3D_STEM_FUSED", "1")
+
+
 def _t3(v):
     return tuple(v) if isinstance(v, (list, tuple)) else (v, v, v)
 
@@ -36,11 +41,18 @@ class X3DStem(HipModule):
 
     def _pack(self):
         cxy, ct = self.conv_xy, self.conv
+        fused = None
+        if tuple(cxy.stride) == (1, 2, 2) and tuple(cxy.padding) == (0, 1, 1) and tuple(ct.stride) == (1, 1, 1) \
+                and tuple(ct.padding) == (2, 0, 0):
+            fused = E.pack_x3d_stem(cxy.weight, ct.weight, self.bn)
         return (E.pack_conv(cxy.weight, None, None, cxy.stride, cxy.padding, E.ACT_NONE),
-                E.pack_dwconv(ct.weight, None, self.bn, ct.stride, ct.padding, E.ACT_RELU))
+                E.pack_dwconv(ct.weight, None, self.bn, ct.stride, ct.padding, E.ACT_RELU), fused)
 
     def run(self, x):
-        pxy, pt = self.pk
+        pxy, pt, fused = self.pk
+        # one launch, the conv_xy result stays in registers (csrc/x3d_head.hip); STEM_FUSED is looked at per call
+        if STEM_FUSED != "0" and E.x3d_stem_supported(x, fused):
+            return E.x3d_stem(x, fused)
         return E.dwconv(E.conv(x, pxy), pt)
 
 
@@ -136,6 +148,11 @@ class Swish(nn.Module):
 # MSPI_X3D_FUSE = 0 (never) | 1 (every stride-1 block the kernel covers) | auto (default)
 FUSE_AB = os.environ.get("MSPI_X3D_FUSE", "auto")
 FUSE_MIN_W = 56
+# First block of a stage (`b` has spatial stride 2): the `a` output is 4x the block's result, and csrc/x3d_head.hip keeps it
+# in LDS.  MSPI_X3D_FUSE_S2 = 0 (never) | 1 (every such block the kernel covers) | auto (default): where the OUTPUT is at
+# least FUSE_S2_MIN_W wide -- stage 2 of X3D-L (112x112 -> 56x56), the only HBM-bound part of the path.
+FUSE_S2 = os.environ.get("MSPI_X3D_FUSE_S2", "auto")
+FUSE_S2_MIN_W = int(os.environ.get("MSPI_X3D_FUSE_S2_MIN_W", "56"))      # 28 adds stage 3 (A/B: profiles/r07_x3d_head.txt)
 # Block seam (`c` of block i + `a` of block i+1 in one launch, csrc/mlp_fused.hip): MSPI_X3D_SEAM = 0 switches it off (A/B)
 SEAM = os.environ.get("MSPI_X3D_SEAM", "1")
 
@@ -170,6 +187,8 @@ class X3DTransform(HipModule):
         }
         # stride-1 blocks: `a` + `b` as one launch, the 2.25x-wide tensor between them stays in LDS (csrc/x3d_block.hip)
         pk["ab"] = E.pack_x3d_ab(pk["a"], pk["b"]) if FUSE_AB != "0" else None
+        # the stage's first block: the same pair with `b` at spatial stride 2 (csrc/x3d_head.hip); FUSE_S2 is looked at per call
+        pk["ab_s2"] = E.pack_x3d_ab_s2(pk["a"], pk["b"])
         if has_se:
             f, c = self.se.fc1.out_channels, self.se.fc1.in_channels
             dev = self.se.fc1.weight.device
@@ -186,6 +205,12 @@ class X3DTransform(HipModule):
         pk = self.pk
         return pk["ab"] is not None and (FUSE_AB == "1" or x.W >= FUSE_MIN_W) and E.x3d_ab_supported(x, pk["ab"])
 
+    def uses_ab_s2(self, x):
+        """Whether run(x) takes the stride-2 fused a + b kernel."""
+        pk = self.pk
+        return pk["ab_s2"] is not None and FUSE_S2 != "0" and (FUSE_S2 == "1" or x.W // 2 >= FUSE_S2_MIN_W) \
+            and E.x3d_ab_s2_supported(x, pk["ab_s2"])
+
     def run(self, x, res, out=None, t=None, seam=None):
         """res: skip tensor added before the final ReLU.
         t: relu(a_bn(a(x))), when the previous block's seam launch already produced it.
@@ -195,6 +220,8 @@ class X3DTransform(HipModule):
         # the fused kernel is built from `a`'s f16x3 planes: it follows that pack's first-sight range check
         if t is None and self.uses_ab(x) and E.range_check_input(pk["a"], x):
             u = E.x3d_ab(x, pk["ab"], pool=se)
+        elif t is None and self.uses_ab_s2(x) and E.range_check_input(pk["a"], x):
+            u = E.x3d_ab_s2(x, pk["ab_s2"], pool=se)
         else:
             u = E.dwconv(E.conv(x, pk["a"]) if t is None else t, pk["b"], pool=se)
         gate = None

@@ -571,6 +571,103 @@ def x3d_ab(x, pk, pool=False):
     return (out, part) if pool else out
 
 
+def pack_x3d_ab_s2(pa, pb):
+    """Operands of the stride-2 fused X3D `a` + `b` kernel (mspi_x3d_ab_s2_fwd, the first block of a stage): the same pack as
+    pack_x3d_ab, from a depthwise conv `pb` with stride (1,2,2); None when the layer pair is outside the kernel's range."""
+    if pb.stride != (1, 2, 2) or (pa.cin_s + 31) // 32 > 3:
+        return None
+    s1 = PackedDw()
+    for f in PackedDw.__slots__:
+        setattr(s1, f, getattr(pb, f))
+    s1.stride = (1, 1, 1)
+    return pack_x3d_ab(pa, s1)
+
+
+def _x3d_ab_s2_desc(x, pk, out_ld, act):
+    d = _lib.X3dAbS2Desc()
+    d.N, d.T, d.H, d.W = x.N, x.T, x.H, x.W
+    d.Cin, d.Cmid, d.ldx, d.ldu, d.act, d.wa_scale = pk.cin_s, pk.cmid_s, x.ld, out_ld, act, pk.wa_scale
+    return d
+
+
+def x3d_ab_s2_supported(x, pk):
+    return pk is not None and x.dense and x.Cs == pk.cin_s \
+        and bool(_lib.load().mspi_x3d_ab_s2_supported(C.byref(_x3d_ab_s2_desc(x, pk, pk.cmid_s, ACT_NONE))))
+
+
+def x3d_ab_s2(x, pk, pool=False, out=None):
+    """u = act(b_bn(dw3x3x3 stride (1,2,2)(relu(a_bn(a(x)))))) in one launch (csrc/x3d_head.hip); pool=True: no activation,
+    also returns the [N, rows, C] partial sums of u for the squeeze-excite gate; otherwise act = Swish."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    if not x3d_ab_s2_supported(x, pk):
+        raise MspiError("x3d_ab_s2: input %s with %d channels is outside the fused kernel's range" % ((x.N, x.T, x.H, x.W), x.C))
+    if out is None:
+        out = alloc(x.N, x.T, x.H // 2, x.W // 2, pk.cmid, x.buf.device)
+    elif (out.N, out.T, out.H, out.W, out.Cs) != (x.N, x.T, x.H // 2, x.W // 2, pk.cmid_s) or not out.dense:
+        raise MspiError("x3d_ab_s2: the output tensor does not match the layer")
+    d = _x3d_ab_s2_desc(x, pk, out.ld, ACT_NONE if pool else ACT_SWISH)
+    part = None
+    if pool:
+        rows = lib.mspi_x3d_ab_s2_pool_rows(C.byref(d))
+        part = torch.empty(x.N, rows, pk.cmid_s, dtype=torch.float32, device=x.buf.device)
+    with _Timed("x3d_ab_s2_pool" if pool else "x3d_ab_s2", 2.0 * x.M * pk.cin_s * pk.cmid + 2.0 * out.M * 27 * pk.cmid,
+                4.0 * (x.M * x.C + out.M * pk.cmid), "in=%s Cin=%d Cmid=%d" % ((x.N, x.T, x.H, x.W), x.C, pk.cmid)):
+        check(lib.mspi_x3d_ab_s2_fwd(C.byref(d), x.ptr, pk.wa.data_ptr(), pk.ba.data_ptr(), pk.wb.data_ptr(), pk.bb.data_ptr(),
+                                     out.ptr, part.data_ptr() if pool else None, _stream()), "mspi_x3d_ab_s2_fwd")
+    return (out, part) if pool else out
+
+
+class PackedX3dStem:
+    __slots__ = ("wxy", "wt", "bias")
+
+
+def pack_x3d_stem(w_xy, w_t, bn):
+    """Operands of the fused X3D stem (mspi_x3d_stem_fwd): conv_xy's weight [24,3,1,3,3] (no bias) and the temporal depthwise
+    weight [24,1,5,1,1] with `bn` folded, as HOST arrays (they travel as kernel arguments); None for any other stem."""
+    if tuple(w_xy.shape) != (24, 3, 1, 3, 3) or tuple(w_t.shape) != (24, 1, 5, 1, 1):
+        return None
+    wt, b = fold_bn(w_t, None, bn)
+    p = PackedX3dStem()
+    p.wxy = w_xy.detach().float().cpu().reshape(24, 27).t().contiguous()      # [(ci,kh,kw)][c]
+    p.wt = wt.detach().float().cpu().reshape(24, 5).t().contiguous()          # [kt][c]
+    p.bias = (b if b is not None else torch.zeros(24)).detach().float().cpu().contiguous()
+    return p
+
+
+def _x3d_stem_desc(x, ldy):
+    d = _lib.X3dStemDesc()
+    d.N, _, d.T, d.H, d.W = x.shape
+    d.sN, d.sC, d.sT, d.sH, d.sW = x.stride()
+    d.ldy = ldy
+    return d
+
+
+def x3d_stem_supported(x, pk):
+    return pk is not None and isinstance(x, torch.Tensor) and x.dim() == 5 and x.shape[1] == 3 and x.dtype == torch.float32 \
+        and x.data_ptr() % 4 == 0 and bool(_lib.load().mspi_x3d_stem_supported(C.byref(_x3d_stem_desc(x, 24))))
+
+
+def x3d_stem(x, pk, out=None):
+    """relu(bn(temporal dw (5,1,1)(conv_xy (1,3,3)/(1,2,2)(x)))) of the raw clip x [N,3,T,H,W] (any strides) in one launch
+    (csrc/x3d_head.hip): the 24-channel conv_xy result stays in registers."""
+    lib = _lib.load()
+    _need_gpu(x)
+    if not x3d_stem_supported(x, pk):
+        raise MspiError("x3d_stem: input %s is outside the fused stem's range" % (tuple(x.shape),))
+    N, _, T, H, W = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is None:
+        out = alloc(N, T, Ho, Wo, 24, x.device)
+    elif (out.N, out.T, out.H, out.W, out.Cs) != (N, T, Ho, Wo, 24) or not out.dense:
+        raise MspiError("x3d_stem: the output tensor does not match the layer")
+    d = _x3d_stem_desc(x, out.ld)
+    with _Timed("x3d_stem", 2.0 * out.M * 24 * (27 + 5), 4.0 * (N * 3 * T * H * W + out.M * 24), "in=%s" % (tuple(x.shape),)):
+        check(lib.mspi_x3d_stem_fwd(C.byref(d), x.data_ptr(), pk.wxy.data_ptr(), pk.wt.data_ptr(), pk.bias.data_ptr(), out.ptr,
+                                    _stream()), "mspi_x3d_stem_fwd")
+    return out
+
+
 class PackedX3dCa:
     __slots__ = ("w", "bc", "ba", "d", "cx", "cx_s", "d_s", "wc_scale", "wa_scale")
 
