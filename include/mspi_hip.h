@@ -624,6 +624,26 @@ int mspi_saliency_sauc_counts(const float* sal, const float* gt, const float* ot
 int mspi_saliency_ig(const float* pred, const float* gt, const float* base, float* out /*[N]*/, int32_t N, int32_t L,
                      mspi_stream_t stream);
 
+/* The training criterion with its gradient (utils/loss.py:26-49: kl - cc [- 0.1 nss] of the model's LOG map).
+ * mspi_saliency_loss_fwd writes the four per-sample values of mspi_saliency_metrics(..., pred_is_log = 1) to terms
+ * (fix NULL: NSS is written as 0) and leaves the per-sample statistics of the backward in ws.  Each sample is split over
+ * chunks of 2048 values on a (chunks, N) grid: pass one writes per-chunk sums, ranges and chunk-centred moments, pass two
+ * merges them about the sample mean and writes the KL / SIM sums, a one-wave launch per sample finishes.  Partials are
+ * combined in a fixed order, no float atomics: bitwise repeatable.
+ * mspi_saliency_loss_bwd is one element-wise pass:
+ *   dlog = *grad_out * d(w_kl KL - w_cc CC - w_nss NSS) / d logmap,
+ * every sample with the same weights (the caller folds the 1/N of a batch mean into them); fix NULL or w_nss == 0 drops the
+ * NSS term and its load.  grad_out is a DEVICE scalar read by the kernel.  logmap / gt / fix must be the arrays the forward
+ * saw.  16-byte loads and stores on every row whose base is 16-byte aligned in all arrays, 4-byte ones on the others.
+ * Neither call synchronises or allocates (graph capture safe).  ws: mspi_saliency_loss_ws_bytes(N, L) bytes of device
+ * scratch, 16-byte aligned; the query is host arithmetic, 0 for N <= 0 or L <= 1.  N <= 65535. */
+size_t mspi_saliency_loss_ws_bytes(int32_t N, int32_t L);
+int mspi_saliency_loss_fwd(const float* logmap, const float* gt, const float* fix /*may be NULL*/, float* terms /*[N][4]*/,
+                           void* ws, int32_t N, int32_t L, mspi_stream_t stream);
+int mspi_saliency_loss_bwd(const float* logmap, const float* gt, const float* fix /*may be NULL*/, const void* ws,
+                           const float* grad_out /*device scalar*/, float w_kl, float w_cc, float w_nss, float* dlog /*[N][L]*/,
+                           int32_t N, int32_t L, mspi_stream_t stream);
+
 /* Bilinear resize of N maps [H][W] -> [Ho][Wo], what upstream does with cv2.resize(..., INTER_LINEAR default) when it brings
  * the prediction to the fixation map's size (utils/compute_saliency_metrics.py:119-122) and the density to the model's size
  * (avsp_dataloader.py:176).  src is uint8 (src_is_u8 != 0: a decoded image, values used as 0..255, unscaled) or float; dst is

@@ -216,6 +216,9 @@ _SIGNATURES = {
     "mspi_saliency_auc_judd": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "mspi_saliency_sauc_counts": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mspi_saliency_ig": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "mspi_saliency_loss_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "mspi_saliency_loss_fwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "mspi_saliency_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, C.c_int32, C.c_int32, _P]),
     "mspi_resize_bilinear_fwd": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mspi_resize_fixation_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mspi_rowgemm_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),

@@ -3,7 +3,8 @@ functions `kldiv`, `cc`, `similarity`, `nss` (same names, same [B,H,W] arguments
 bookkeeping of `utils/loss.py:SalLoss` -- all four metrics of a batch come from ONE launch of mspi_saliency_metrics.
 `auc_judd`, `auc_shuff` and `ig` (:111-308 of the same file) have launches of their own; `SalEval` keeps all seven and
 `validation_one_epoch` is the loop of the reference's `engine_train.py:84-125`.
-Evaluation only (no autograd); there is no CPU fallback."""
+The criterion is differentiable with respect to the log map (sal_loss, sal_loss_terms, SalLoss on an input that requires
+grad: csrc/salloss.hip); everything else is evaluation only.  There is no CPU fallback."""
 import ctypes as C
 import math
 
@@ -176,9 +177,113 @@ class _Avg:
         return self.sum / max(self.count, 1)
 
 
+SAL_LOSS_CHUNK = 2048      # values per workgroup of mspi_saliency_loss_fwd (csrc/salloss.hip SL_C)
+
+
+def _loss_fwd(x, g, f):
+    """(terms [B,4], ws) of one mspi_saliency_loss_fwd; x / g / f: contiguous float32 [B,H,W] CUDA tensors (f may be None)."""
+    lib = _lib.load()
+    B, L = x.shape[0], x.shape[1] * x.shape[2]
+    terms = torch.empty(B, 4, dtype=torch.float32, device=x.device)
+    ws = torch.empty(lib.mspi_saliency_loss_ws_bytes(B, L), dtype=torch.uint8, device=x.device)
+    check(lib.mspi_saliency_loss_fwd(x.data_ptr(), g.data_ptr(), None if f is None else f.data_ptr(), terms.data_ptr(),
+                                     ws.data_ptr(), B, L, _stream()), "mspi_saliency_loss_fwd")
+    return terms, ws
+
+
+def _loss_bwd(x, g, f, ws, grad_out, w_kl, w_cc, w_nss):
+    """dlog [B,H,W] of one mspi_saliency_loss_bwd; grad_out: a float32 scalar on the device."""
+    lib = _lib.load()
+    B, L = x.shape[0], x.shape[1] * x.shape[2]
+    go = grad_out.to(torch.float32).contiguous()
+    dlog = torch.empty_like(x)
+    check(lib.mspi_saliency_loss_bwd(x.data_ptr(), g.data_ptr(), None if f is None else f.data_ptr(), ws.data_ptr(), go.data_ptr(),
+                                     w_kl, w_cc, w_nss, dlog.data_ptr(), B, L, _stream()), "mspi_saliency_loss_bwd")
+    return dlog
+
+
+def _no_double_backward():
+    if torch.is_grad_enabled():        # the engine enables grad inside backward only for create_graph=True
+        raise MspiError("mspi_amd.metrics: the saliency loss has no double backward (create_graph=True is not supported)")
+
+
+def _loss_inputs(what, log_map, density, fixations):
+    if not torch.is_tensor(log_map) or log_map.dtype != torch.float32:
+        raise MspiError("%s: the log map must be a float32 tensor" % what)
+    maps = _maps(what, log_map, density) if fixations is None else _maps(what, log_map, density, fixations)
+    return maps[0], maps[1], (maps[2] if fixations is not None else None)
+
+
+class _SalLossFn(torch.autograd.Function):
+    """loss = sum_n (w_kl KL_n - w_cc CC_n - w_nss NSS_n) and the [B,4] terms (not differentiable here: the loss carries
+    the gradient), one forward and one backward launch group.  The gradient goes to the log map only."""
+
+    @staticmethod
+    def forward(ctx, log_map, density, fixations, w_kl, w_cc, w_nss):
+        x, g, f = _loss_inputs("sal_loss", log_map, density, fixations)
+        terms, ws = _loss_fwd(x, g, f)
+        t = terms.sum(0)
+        loss = t[0] * w_kl - t[1] * w_cc
+        if f is not None:
+            loss = loss - t[3] * w_nss
+        ctx.save_for_backward(x, g, f, ws)
+        ctx.weights = (float(w_kl), float(w_cc), float(w_nss) if f is not None else 0.0)
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms):
+        _no_double_backward()
+        x, g, f, ws = ctx.saved_tensors
+        return _loss_bwd(x, g, f, ws, grad_loss, *ctx.weights), None, None, None, None, None
+
+
+class _SalTermsFn(torch.autograd.Function):
+    """The [B,4] terms with a gradient of their own: any weighting per sample and term.  The kernel takes one device scalar
+    and three host weights, so the backward is one launch per term (KL, CC, NSS) scaled by that term's column of the
+    incoming gradient.  SIM is a reported value without a gradient, as in the loss."""
+
+    @staticmethod
+    def forward(ctx, log_map, density, fixations):
+        x, g, f = _loss_inputs("sal_loss_terms", log_map, density, fixations)
+        terms, ws = _loss_fwd(x, g, f)
+        ctx.save_for_backward(x, g, f, ws)
+        return terms
+
+    @staticmethod
+    def backward(ctx, grad_terms):
+        _no_double_backward()
+        x, g, f, ws = ctx.saved_tensors
+        one = torch.ones((), dtype=torch.float32, device=x.device)
+        out = None
+        for col, w in ((0, (1.0, 0.0, 0.0)), (1, (0.0, -1.0, 0.0)), (3, (0.0, 0.0, -1.0))):
+            if col == 3 and f is None:
+                continue
+            d = _loss_bwd(x, g, f, ws, one, *w).mul_(grad_terms[:, col].to(torch.float32).view(-1, 1, 1))
+            out = d if out is None else out.add_(d)
+        return out, None, None
+
+
+def sal_loss(log_map, density, fixations=None, w_kl=1.0, w_cc=1.0, w_nss=0.1):
+    """(loss, terms): loss = mean over the batch of w_kl KL - w_cc CC [- w_nss NSS] as a 0-dim device tensor with a
+    grad_fn, terms the [B,4] per-sample (KL, CC, SIM, NSS) without one.  No host synchronisation: the pair of launches can
+    be captured in a graph.  Non-contiguous inputs are made contiguous; the gradient comes back in the input's shape."""
+    B = log_map.shape[0] if torch.is_tensor(log_map) and log_map.dim() else 1
+    return _SalLossFn.apply(log_map, density, fixations, w_kl / B, w_cc / B, w_nss / B)
+
+
+def sal_loss_terms(log_map, density, fixations=None):
+    """[B,4] per-sample (KL, CC, SIM, NSS) of a log map, connected to the graph: the values of
+    per_sample(..., pred_is_log=True) from the chunked kernels, differentiable with respect to the log map in the KL, CC
+    and NSS columns (SIM counts as a constant)."""
+    return _SalTermsFn.apply(log_map, density, fixations)
+
+
 class SalLoss:
-    """utils/loss.py:6-49 for evaluation: forward(log_map, density[, fixations]) -> kl - cc [- 0.1 nss], with running
-    averages of every term in .log (timm's AverageMeter upstream)."""
+    """utils/loss.py:6-49: forward(log_map, density[, fixations]) -> kl - cc [- 0.1 nss], with running averages of every
+    term in .log (timm's AverageMeter upstream).  With grad enabled and a log map that requires grad the result is a
+    0-dim device tensor with a grad_fn (sal_loss: hand-written forward and backward kernels); otherwise it is the
+    evaluation path, one launch of mspi_saliency_metrics and a tensor without a graph."""
 
     def __init__(self):
         self.reset_records()
@@ -187,8 +292,13 @@ class SalLoss:
         self.log = {k: _Avg() for k in ("kl", "cc", "sim", "nss", "loss")}
 
     def forward(self, inputs, targets, fixations=None, targets2=None):
-        m = per_sample(inputs, targets, fix=fixations, pred_is_log=True).mean(0)
-        kl, c, sim, ns = (float(v) for v in m.tolist())
+        graph = torch.is_grad_enabled() and torch.is_tensor(inputs) and inputs.requires_grad
+        if graph:
+            out, terms = sal_loss(inputs, targets, fixations)
+            m = terms.mean(0)
+        else:
+            m = per_sample(inputs, targets, fix=fixations, pred_is_log=True).mean(0)
+        kl, c, sim, ns = (float(v) for v in m.tolist())          # the one host read (upstream's .item() calls)
         loss = kl - c - (0.1 * ns if fixations is not None else 0.0)
         self.log["kl"].update(kl)
         self.log["cc"].update(c)
@@ -196,7 +306,7 @@ class SalLoss:
         if fixations is not None:
             self.log["nss"].update(ns)
         self.log["loss"].update(loss)
-        return torch.tensor(loss, device=inputs.device)
+        return out if graph else torch.tensor(loss, device=inputs.device)
 
     __call__ = forward
 
