@@ -644,6 +644,47 @@ int mspi_saliency_loss_bwd(const float* logmap, const float* gt, const float* fi
                            const float* grad_out /*device scalar*/, float w_kl, float w_cc, float w_nss, float* dlog /*[N][L]*/,
                            int32_t N, int32_t L, mspi_stream_t stream);
 
+/* Backward of the decoder's readout tail (csrc/readout_bwd.hip): conv (4,1,1)/4 64 -> 32, x4 bilinear up-sample + ReLU,
+ * conv (1,3,3) 32 -> 32 + ReLU, conv (1,3,3) 32 -> 1, x - logsumexp(x).  Sums that cross a workgroup go through the caller's
+ * workspace as per-workgroup records and a second launch adds the records in a fixed order: no float atomics, bitwise
+ * repeatable.  No call allocates or synchronises.  Workspaces are device scratch, 16-byte aligned.
+ *
+ * mspi_logsumexp_sub_bwd: dz[n][i] = g[n][i] - exp(logp[n][i]) * sum_i g[n][i]; logp is the forward's output.  One
+ * workgroup per sample.
+ *
+ * mspi_conv_c1_bwd: the last conv (1,3,3) pad (0,1,1) C -> 1 and the ReLU in front of it, one pass over y [M = N*H*W][C]
+ * (the saved post-ReLU activations, row stride ldy), dz [N][H][W], w [9][C] (tap (kh,kw), channel fastest):
+ *   d[p][c]    = (y[p][c] > 0) * sum_tap dz[p - tap] * w[tap][c]     (row stride ldd; zero padding per image)
+ *   dW[tap][c] = sum_p dz[p - tap] * y[p][c],   db[0] = sum dz
+ * Workgroups of 1024 rows; ws: mspi_conv_c1_bwd_ws_bytes(N, H, W) bytes (host arithmetic, 0 for an empty extent).
+ * C % 4 == 0, C <= 64; y, d, w 16-byte aligned, ldy and ldd multiples of 4.
+ *
+ * mspi_conv_wgrad_fwd: weight gradient of the convolution `d` describes (the forward's descriptor; ldy = row stride of dy,
+ * the weight, activation and precision members are not read): dW[co][(kt,kh,kw,ci)] = sum_m dy[m][co] * x[pos(m, tap)][ci]
+ * dense [Cout][kT*kH*kW*C] fp32 (the row order of the forward's weights, unscaled) and db[co] = sum_m dy[m][co].  The rows
+ * are the contraction of v_mfma_f32_32x32x2_f32 (an exact fp32 fmaf chain); they are split into slices of 256 rows, 2048
+ * from 65536 rows on, one slice and three (tap, 32-channel) tiles per workgroup.  Supported: stored Cout <= 32 and C <= 64,
+ * both multiples of 4, at most 27 taps, sC == 1, fewer than 2^31 rows, x and dy 16-byte aligned.
+ * mspi_conv_wgrad_supported: 1 or 0 for the descriptor alone; mspi_conv_wgrad_variant: the slice length in rows, or -1 for
+ * exactly what the launch refuses (descriptor or pointers), the reason in mspi_last_error(); mspi_conv_wgrad_ws_bytes: host
+ * arithmetic, 0 for a refused descriptor.
+ *
+ * mspi_upsample_bwd: adjoint of mspi_upsample_fwd (same factor, source coordinates and edge clamping): dx [NT][H][W][C] from
+ * dy [NT][H*factor][W*factor][C], one thread per source vector gathering the <= 2 factor x 2 factor destination cells that
+ * tap it.  act == MSPI_ACT_RELU: u is the forward's output (row stride ldu) and cells with u <= 0 are skipped -- the mask
+ * of the ReLU in the forward's epilogue; MSPI_ACT_NONE: u is not read.  C % 4 == 0, factor 2, 4 or 8. */
+int mspi_logsumexp_sub_bwd(const float* logp, const float* g, float* dz, int32_t N, int32_t L, mspi_stream_t stream);
+size_t mspi_conv_c1_bwd_ws_bytes(int32_t N, int32_t H, int32_t W);
+int mspi_conv_c1_bwd(const float* y, int64_t ldy, const float* dz, const float* w, float* d, int64_t ldd, float* dW /*[9][C]*/,
+                     float* db /*[1]*/, void* ws, int32_t N, int32_t H, int32_t W, int32_t C, mspi_stream_t stream);
+int mspi_conv_wgrad_supported(const MspiConvDesc* d);
+size_t mspi_conv_wgrad_ws_bytes(const MspiConvDesc* d);
+int mspi_conv_wgrad_variant(const MspiConvDesc* d, const void* x, const void* dy);
+int mspi_conv_wgrad_fwd(const MspiConvDesc* d, const float* x, const float* dy, float* dW, float* db, void* ws,
+                        mspi_stream_t stream);
+int mspi_upsample_bwd(const float* dy, int64_t ldy, const float* u /*NULL without ReLU*/, int64_t ldu, float* dx, int64_t ldx,
+                      int32_t NT, int32_t H, int32_t W, int32_t C, int32_t factor, int32_t act, mspi_stream_t stream);
+
 /* Bilinear resize of N maps [H][W] -> [Ho][Wo], what upstream does with cv2.resize(..., INTER_LINEAR default) when it brings
  * the prediction to the fixation map's size (utils/compute_saliency_metrics.py:119-122) and the density to the model's size
  * (avsp_dataloader.py:176).  src is uint8 (src_is_u8 != 0: a decoded image, values used as 0..255, unscaled) or float; dst is

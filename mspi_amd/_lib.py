@@ -219,6 +219,15 @@ _SIGNATURES = {
     "mspi_saliency_loss_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mspi_saliency_loss_fwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "mspi_saliency_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, C.c_int32, C.c_int32, _P]),
+    "mspi_logsumexp_sub_bwd": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "mspi_conv_c1_bwd_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "mspi_conv_c1_bwd": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mspi_conv_wgrad_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "mspi_conv_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "mspi_conv_wgrad_variant": (C.c_int, [C.POINTER(ConvDesc), _P, _P]),
+    "mspi_conv_wgrad_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
+    "mspi_upsample_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, _P]),
     "mspi_resize_bilinear_fwd": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mspi_resize_fixation_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mspi_rowgemm_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),

@@ -25,7 +25,7 @@ DEFAULT_PREC = {"f32": PREC_F32, "f16x3": PREC_F16X3}[_os.environ.get("MSPI_GEMM
 
 __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedConv", "PackedDw", "conv", "dwconv", "maxpool",
            "layernorm", "attention", "upsample", "upsample_sum", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine",
-           "se_gate", "add", "fold_bn", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "se_gate", "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 def rup4(c):
@@ -1310,6 +1310,115 @@ def logsumexp_sub(t, N, L):
     lib = _lib.load()
     check(lib.mspi_logsumexp_sub(t.data_ptr(), N, L, _stream()), "mspi_logsumexp_sub")
     return t
+
+
+# ----------------------------------------------------------------------------- readout tail backward (csrc/readout_bwd.hip)
+WGRAD_SLICES = (256, 2048)      # rows per slice of mspi_conv_wgrad_fwd: the codes mspi_conv_wgrad_variant answers
+WGRAD_BIG_M = 65536             # rows from which the long slice is taken
+C1_BWD_ROWS = 1024              # rows per workgroup of mspi_conv_c1_bwd
+
+
+def logsumexp_sub_bwd(logp, g, dz=None):
+    """dz = g - exp(logp) * sum(g) per sample: backward of logsumexp_sub.  logp (the forward's output) and g are [N, ...]
+    fp32 tensors of one shape."""
+    lib = _lib.load()
+    _need_gpu(logp)
+    if logp.shape != g.shape or logp.dim() < 2 or logp.dtype != torch.float32 or g.dtype != torch.float32 or g.device != logp.device:
+        raise MspiError("logsumexp_sub_bwd: logp %s / g %s must be fp32 tensors of one shape on one device" % (tuple(logp.shape), tuple(g.shape)))
+    logp, g = logp.contiguous(), g.contiguous()
+    N = logp.shape[0]
+    if dz is None:
+        dz = torch.empty_like(logp)
+    with _Timed("logsumexp_sub_bwd", 0.0, 12.0 * logp.numel()):
+        check(lib.mspi_logsumexp_sub_bwd(logp.data_ptr(), g.data_ptr(), dz.data_ptr(), N, logp.numel() // N, _stream()),
+              "mspi_logsumexp_sub_bwd")
+    return dz
+
+
+def conv_c1_bwd(y, dz, weight):
+    """Backward of the last conv (1,3,3) pad (0,1,1) C -> 1 and of the ReLU that produced its input.  y: CL [N,1,H,W,C], the
+    saved post-ReLU activations; dz [N,H,W]; weight: the parameter [1,C,1,3,3].  Returns (d, dW, db): d a CL like y, the
+    gradient in front of the ReLU; dW [1,C,1,3,3] and db [1] in the parameter's layout."""
+    lib = _lib.load()
+    _need_gpu(y.buf)
+    Cc = y.Cs
+    if y.T != 1 or not y.dense or tuple(dz.shape) != (y.N, y.H, y.W) or dz.dtype != torch.float32 or dz.device != y.buf.device:
+        raise MspiError("conv_c1_bwd: y %s and dz %s do not match" % ((y.N, y.T, y.H, y.W, y.C), tuple(dz.shape)))
+    if tuple(weight.shape) != (1, y.C, 1, 3, 3) or Cc != y.C or Cc > 64:
+        raise MspiError("conv_c1_bwd: weight %s is not a (1,3,3) conv from %d channels (a multiple of 4, at most 64) to 1"
+                        % (tuple(weight.shape), y.C))
+    dev = y.buf.device
+    dz = dz.contiguous()
+    w = weight.detach().float().reshape(Cc, 9).t().contiguous().to(dev)          # [tap][c]
+    d = alloc(y.N, 1, y.H, y.W, y.C, dev)
+    dW = torch.empty(9, Cc, dtype=torch.float32, device=dev)
+    db = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_conv_c1_bwd_ws_bytes(y.N, y.H, y.W) // 4, dtype=torch.float32, device=dev)   # stream-ordered
+    with _Timed("conv_c1_bwd", 4.0 * y.M * 9 * Cc, 8.0 * y.M * Cc, "M=%d C=%d" % (y.M, Cc)):
+        check(lib.mspi_conv_c1_bwd(y.ptr, y.ld, dz.data_ptr(), w.data_ptr(), d.ptr, d.ld, dW.data_ptr(), db.data_ptr(),
+                                   ws.data_ptr(), y.N, y.H, y.W, Cc, _stream()), "mspi_conv_c1_bwd")
+    return d, dW.t().reshape(1, Cc, 1, 3, 3), db
+
+
+def _wgrad_desc(x, dy, pk):
+    To, Ho, Wo = _out_extent(x.T, x.H, x.W, pk.k, pk.stride, pk.pad)
+    d = ConvDesc()
+    d.N, d.T, d.H, d.W, d.C = x.N, x.T, x.H, x.W, x.Cs
+    d.sN, d.sT, d.sH, d.sW, d.sC = x.sN, x.H * x.W * x.ld, x.W * x.ld, x.ld, 1
+    d.kT, d.kH, d.kW = pk.k
+    d.strT, d.strH, d.strW = pk.stride
+    d.padT, d.padH, d.padW = pk.pad
+    d.To, d.Ho, d.Wo = To, Ho, Wo
+    d.Cout, d.ldy = pk.cout_s, dy.ld
+    return d
+
+
+def conv_wgrad_variant(x, dy, pk):
+    """The instantiation conv_wgrad(x, dy, pk) launches (rows per slice), -1 where it refuses; host only."""
+    return _lib.load().mspi_conv_wgrad_variant(C.byref(_wgrad_desc(x, dy, pk)), x.ptr, dy.ptr)
+
+
+def conv_wgrad(x, dy, pk):
+    """Weight and bias gradient of conv(x, pk) for the output gradient dy (CL, one row per output position, in front of any
+    activation).  Returns (dW, db) in the parameter's own layout, [Co,Ci,kt,kh,kw] and [Co]."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    if x.Cs != pk.cin_s or dy.Cs != pk.cout_s:
+        raise MspiError("conv_wgrad: x has %d / dy %d stored channels, the layer %d -> %d" % (x.Cs, dy.Cs, pk.cin_s, pk.cout_s))
+    d = _wgrad_desc(x, dy, pk)
+    if not dy.dense or dy.M != x.N * d.To * d.Ho * d.Wo or dy.buf.device != x.buf.device:
+        raise MspiError("conv_wgrad: dy has %d rows, the layer's output %d (or dy is not dense)" % (dy.M, x.N * d.To * d.Ho * d.Wo))
+    if lib.mspi_conv_wgrad_variant(C.byref(d), x.ptr, dy.ptr) < 0:
+        raise MspiError("conv_wgrad: %s" % lib.mspi_last_error().decode("utf-8", "replace"))
+    dev = x.buf.device
+    kt, kh, kw = pk.k
+    dW = torch.empty(pk.cout_s, kt, kh, kw, pk.cin_s, dtype=torch.float32, device=dev)
+    db = torch.empty(pk.cout_s, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_conv_wgrad_ws_bytes(C.byref(d)) // 4, dtype=torch.float32, device=dev)   # stream-ordered
+    taps = kt * kh * kw
+    with _Timed("conv_wgrad", 2.0 * dy.M * taps * pk.cin * pk.cout, 4.0 * (x.M * pk.cin + dy.M * pk.cout),
+                "M=%d K=%d(%dx%d) N=%d" % (dy.M, taps * pk.cin, taps, pk.cin, pk.cout)):
+        check(lib.mspi_conv_wgrad_fwd(C.byref(d), x.ptr, dy.ptr, dW.data_ptr(), db.data_ptr(), ws.data_ptr(), _stream()),
+              "mspi_conv_wgrad_fwd")
+    return dW[:pk.cout, :, :, :, :pk.cin].permute(0, 4, 1, 2, 3), db[:pk.cout]
+
+
+def upsample_bwd(dy, factor, u=None, act=ACT_NONE):
+    """Adjoint of upsample(src, factor, act=act): dy is the gradient of the up-sampled CL; with act == ACT_RELU, u is the
+    forward's output and supplies the ReLU mask.  Returns the gradient of src."""
+    lib = _lib.load()
+    _need_gpu(dy.buf)
+    if factor not in (2, 4, 8) or dy.H % factor or dy.W % factor or not dy.dense:
+        raise MspiError("upsample_bwd: factor %s must be 2, 4 or 8 and divide the dense gradient's %d x %d" % (factor, dy.H, dy.W))
+    if act not in (ACT_NONE, ACT_RELU) or (act == ACT_RELU) != (u is not None):
+        raise MspiError("upsample_bwd: act is ACT_NONE without u, or ACT_RELU with the forward's output u")
+    if u is not None and ((u.N, u.T, u.H, u.W, u.Cs) != (dy.N, dy.T, dy.H, dy.W, dy.Cs) or not u.dense or u.buf.device != dy.buf.device):
+        raise MspiError("upsample_bwd: u does not match the gradient")
+    dx = alloc(dy.N, dy.T, dy.H // factor, dy.W // factor, dy.C, dy.buf.device)
+    with _Timed("upsample_bwd", 0.0, 4.0 * (dx.M + dy.M * (2 if u is not None else 1)) * dy.C):
+        check(lib.mspi_upsample_bwd(dy.ptr, dy.ld, u.ptr if u is not None else None, u.ld if u is not None else 0, dx.ptr, dx.ld,
+                                    dy.N * dy.T, dx.H, dx.W, dy.Cs, factor, act, _stream()), "mspi_upsample_bwd")
+    return dx
 
 
 def mean_rows(x, N, R, out):

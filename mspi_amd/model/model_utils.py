@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from .. import engine as E
 from .._lib import MspiError
+from ..autograd import ReadoutTail, pack_readout_tail, readout_tail_forward
 from ..backbones.convnext import ConvNeXtTinyFeatures
 from ..backbones.resnet import get_resnet18
 from ..module import HipModule, to_cl
@@ -441,6 +442,7 @@ class _SaliencyBase(HipModule):
             "r8": E.pack_conv(r[8].weight, r[8].bias, None, (4, 1, 1), (0, 0, 0), E.ACT_NONE),
             "r10": E.pack_conv(r[10].weight, r[10].bias, None, (1, 1, 1), (0, 1, 1), E.ACT_RELU),
             "r12": E.pack_conv(r[12].weight, r[12].bias, None, (1, 1, 1), (0, 1, 1), E.ACT_NONE),
+            "tail_key": self._tail_key(),
         }
 
     @staticmethod
@@ -496,9 +498,9 @@ class _SaliencyBase(HipModule):
         """The three SA modules' first convs (same input) as one 512->96 conv."""
         return E.conv(masks, pk["sa_cat"])
 
-    def _fuse_readout(self, pk, cat, s0, s1, s2, s3, masks, pm):
-        """SA gating, top-down fusion and readout (model/model_utils.py:566-572)."""
-        B = s0.N
+    def _fuse_readout(self, pk, cat, s0, s1, s2, s3, masks, pm, features=False):
+        """SA gating, top-down fusion and readout (model/model_utils.py:566-572); features=True stops in front of readout[8]
+        and returns y4 [B,4,h,w,64]."""
         self.sa_2.run(s2, masks, pm.slice(64, 32))
         E.upsample(s3, 2, dst=s2, accumulate=True)
         self.sa_1.run(s1, masks, pm.slice(32, 32))
@@ -520,11 +522,58 @@ class _SaliencyBase(HipModule):
             E.upsample(s2, 4, dst=cat.slice(384, 192))
             E.upsample(s3, 8, dst=cat.slice(576, 192))
             y = E.conv(cat, pk["r0"])
-        y = E.conv(E.conv(y, pk["r1"]), pk["r4"])
-        y = E.upsample(E.conv(y, pk["r8"]), 4, act=E.ACT_RELU)   # == relu(conv(4,1,1)(upsample(y))) of the reference
-        y = E.conv(E.conv(y, pk["r10"]), pk["r12"])              # [B,1,H,W,1], ld 1
-        E.logsumexp_sub(y.buf, B, y.H * y.W)
-        return y.buf.view(B, y.H, y.W)
+        y4 = E.conv(E.conv(y, pk["r1"]), pk["r4"])
+        return y4 if features else self._readout_tail(pk, y4)
+
+    def _readout_tail(self, pk, y4):
+        """readout[8], [10], [12] and the log-softmax on y4 [B,4,h,w,64]: four launches (autograd.readout_tail_forward; the
+        trainable form of the same launches is autograd.ReadoutTail)."""
+        key = self._tail_key()
+        if pk["tail_key"] != key:      # an optimiser has moved the tail in place since the three were packed
+            r = self.readout
+            pk["r8"], pk["r10"], pk["r12"] = pack_readout_tail(r[8].weight, r[8].bias, r[10].weight, r[10].bias,
+                                                               r[12].weight, r[12].bias)
+            pk["tail_key"] = key
+        return readout_tail_forward(y4, pk["r8"], pk["r10"], pk["r12"])[0]
+
+    def _tail_key(self):
+        """Identity and in-place version of the six tail tensors: what the packs r8, r10, r12 were built from."""
+        r = self.readout
+        # _version is torch's private in-place counter, the only record of optimiser steps and of load_state_dict (both write
+        # in place and keep data_ptr); an assignment `p.data = ...` need not bump it but moves data_ptr, which is why the key holds that too
+        return tuple((p.data_ptr(), p._version) for i in (8, 10, 12) for p in (r[i].weight, r[i].bias))
+
+    TAIL_PARAMS = tuple("readout.%d.%s" % (i, n) for i in (8, 10, 12) for n in ("weight", "bias"))
+
+    def trainable(self, what):
+        """trainable("readout_tail"): the three convs readout[8], readout[10], readout[12] become trainable on top of a frozen
+        network -- every other parameter gets requires_grad_(False), and a forward with grad enabled computes the features in
+        front of readout[8] as in inference (eval BatchNorm, folded) and hands them to autograd.ReadoutTail.
+        trainable(None) switches back and restores the flags found at switch-on.  Off by default."""
+        d = self.__dict__
+        if what is None:
+            for p, flag in d.pop("_trainable_saved", []):
+                p.requires_grad_(flag)
+            d["_trainable"] = None
+            return self
+        if what != "readout_tail":
+            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail' is)" % (what,))
+        if d.get("_trainable") is None:
+            d["_trainable_saved"] = [(p, p.requires_grad) for p in self.parameters()]
+        d["_trainable"] = what
+        tail = set(self.TAIL_PARAMS)
+        for name, p in self.named_parameters():
+            p.requires_grad_(name in tail)
+        return self
+
+    def _training_tail(self):
+        """True when this forward goes through autograd.ReadoutTail."""
+        return self.__dict__.get("_trainable") == "readout_tail" and torch.is_grad_enabled()
+
+    def _tail_with_grad(self, y4):
+        r = self.readout
+        y = y4.buf.view(y4.N, y4.T, y4.H, y4.W, y4.ld)
+        return ReadoutTail.apply(y, r[8].weight, r[8].bias, r[10].weight, r[10].bias, r[12].weight, r[12].bias)
 
     def _try_load(self, module_loader, path, what):
         if os.path.exists(path):
@@ -581,6 +630,9 @@ class AudioVisualSaliencyModel(_SaliencyBase):
                        cfg.MODEL.IMAGE_SALIENCY_ENCODER_WEIGHT, "image saliency encoder weights")
 
     def frozen_encoder(self):
+        if self.__dict__.get("_trainable") == "readout_tail":
+            self.eval()      # frozen means folded eval BatchNorm everywhere; the tail has neither BatchNorm nor dropout
+            return
         self.audnet.eval()
         self.image_encoder.eval()
 
@@ -607,10 +659,16 @@ class AudioVisualSaliencyModel(_SaliencyBase):
         y = E.layernorm(E.conv(emb, p[3][0]), p[3][1], p[3][2], 1e-5, act=E.ACT_RELU)
         return emb, E.conv(y, p[4])
 
-    @torch.no_grad()
     def forward(self, clips, audios, frame_feats=None):
         """frame_feats: optional (f1 [B*T,h,w,96], f0 [B*T,h/2,w/2,320]) from encode_frames() for the clips' frames in
-        (b t) order -- the image branch then starts at the adapter (sliding-window inference re-uses 15 of 16 frames)."""
+        (b t) order -- the image branch then starts at the adapter (sliding-window inference re-uses 15 of 16 frames).
+        After trainable("readout_tail") and with grad enabled, the map carries the graph of autograd.ReadoutTail."""
+        tail = self._training_tail()
+        with torch.no_grad():
+            y, loss = self._forward(clips, audios, frame_feats, features=tail)
+        return (self._tail_with_grad(y) if tail else y), loss
+
+    def _forward(self, clips, audios, frame_feats, features):
         self._check_eval()
         pk = self.pk
         clips = clips.float()
@@ -630,7 +688,7 @@ class AudioVisualSaliencyModel(_SaliencyBase):
             cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3)
             fk.join(1)
             s3, loss = self._sync_and_lateral3(pk, v4, aud, fk)
-        return self._fuse_readout(pk, cat, s0, s1, s2, s3, masks, pm), loss
+        return self._fuse_readout(pk, cat, s0, s1, s2, s3, masks, pm, features), loss
 
     def _sync_and_lateral3(self, pk, v4, aud, fk):
         B, dev = v4.N, v4.buf.device
@@ -670,13 +728,21 @@ class VisualSaliencyModel(_SaliencyBase):
                        cfg.MODEL.IMAGE_SALIENCY_ENCODER_WEIGHT, "image saliency encoder weights")
 
     def frozen_encoder(self):
+        if self.__dict__.get("_trainable") == "readout_tail":
+            self.eval()
+            return
         self.image_encoder.eval()
 
     def _pack(self):
         return self._pack_decoder(split=None)
 
-    @torch.no_grad()
     def forward(self, clips, frame_feats=None):
+        tail = self._training_tail()
+        with torch.no_grad():
+            y = self._forward(clips, frame_feats, features=tail)
+        return (self._tail_with_grad(y) if tail else y), 0
+
+    def _forward(self, clips, frame_feats, features):
         self._check_eval()
         pk = self.pk
         clips = clips.float()
@@ -688,4 +754,4 @@ class VisualSaliencyModel(_SaliencyBase):
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
             cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3)
             s3 = self._lateral(pk, 3, [v4])
-        return self._fuse_readout(pk, cat, s0, s1, s2, s3, masks, pm), 0
+        return self._fuse_readout(pk, cat, s0, s1, s2, s3, masks, pm, features)

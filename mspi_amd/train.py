@@ -1,0 +1,126 @@
+"""Fine-tune the readout tail of a checkpoint: the reference's train.py as far as the tail needs it, on the MI355X.
+
+    python -m mspi_amd.train --trainable readout_tail --weights w.pt --dataset AVAD --split 1 --model x3dl
+        [--path_data ./AuViDataset] [--log_dir ./training_logs] [--save_ckpt_freq 10] [--gamma 1] [--start_epoch 0]
+        [--resolution H W] [--batch 2] [--no_sound] [--workers 8]
+
+Only readout[8], readout[10] and readout[12] train (model.trainable("readout_tail")); everything in front of them is frozen and
+runs as in inference, with eval BatchNorm folded into the convolutions.  That is head fine-tuning of a released checkpoint, not
+upstream's full training, where the decoder's BatchNorm layers run on batch statistics.  As upstream: the training split of
+avsp_dataloader.AudioVisualDataset, AdamW over the parameters that require grad with weight decay 0, cfg.SOLVER.LR for 60
+epochs then a tenth of it every 60 (lr_by_epoch), a state_dict checkpoint every --save_ckpt_freq epochs and at the end
+(inference.build_model loads them), one JSON line per epoch, printed and appended to <log_dir>/log.txt.  One process, one GPU."""
+import argparse
+import json
+import os
+
+import torch
+
+from ._lib import MspiError
+
+TRAINABLE = ("readout_tail",)
+
+
+def lr_by_epoch(cfg):
+    """train.py:161-166: cfg.SOLVER.LR for the first 60 epochs, then a tenth of it, divided by ten again every 60 epochs; one
+    value per epoch up to cfg.SOLVER.MAX_EPOCH."""
+    values = [cfg.SOLVER.LR for _ in range(60)]
+    lr = cfg.SOLVER.LR * 0.1
+    for i in range(cfg.SOLVER.MAX_EPOCH - 60):
+        values.append(lr)
+        if (i + 1) % 60 == 0:
+            lr = lr * 0.1
+    return values
+
+
+def _single_rank():
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise MspiError("mspi_amd.train runs on one rank: multi-rank training is not built (WORLD_SIZE=%s)" % os.environ["WORLD_SIZE"])
+
+
+def check_trainable(value):
+    if value not in TRAINABLE:
+        raise MspiError("--trainable %s: only %s can be trained (the models' backward stops in front of readout[8])"
+                        % (value, ", ".join(TRAINABLE)))
+    return value
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(prog="python -m mspi_amd.train", description=__doc__.split("\n")[0])
+    parser.add_argument("--trainable", default="readout_tail", type=str, help="the part of the model that trains: readout_tail")
+    parser.add_argument("--start_epoch", default=0, type=int)
+    parser.add_argument("--split", default=1, type=int)
+    parser.add_argument("--dataset", default="AVAD", type=str)
+    parser.add_argument("--weights", default="", type=str, help="checkpoint to start from (a state_dict)")
+    parser.add_argument("--log_dir", default="./training_logs", type=str)
+    parser.add_argument("--save_ckpt_freq", default=10, type=int)
+    parser.add_argument("--gamma", default=1.0, type=float)
+    parser.add_argument("--path_data", default="./AuViDataset", type=str)
+    parser.add_argument("--model", default=os.environ.get("MSPI_MOTION_ENCODER", "mvitv2s"), type=str)
+    parser.add_argument("--resolution", default=[224, 384], type=int, nargs=2, help="H W the frames are resized to")
+    parser.add_argument("--clip_size", default=16, type=int)
+    parser.add_argument("--batch", default=None, type=int, help="clips per step (default cfg.TRAIN.BATCH_SIZE)")
+    parser.add_argument("--no_sound", dest="use_sound", action="store_false", help="the visual-only model")
+    parser.add_argument("--workers", default=8, type=int, help="host threads decoding JPEGs")
+    parser.add_argument("--seed", default=2023, type=int)
+    return parser
+
+
+def train(model, data, cfg, device, log_dir, start_epoch=0, save_ckpt_freq=10, gamma=1.0):
+    """The epoch loop of train.py:158-200 over `data` (an iterable of device batches).  Returns the per-epoch dicts."""
+    from .engine_train import train_one_epoch
+    from .metrics import SalLoss
+    params = [p for p in model.parameters() if p.requires_grad]
+    if not params:
+        raise MspiError("train: no parameter requires grad; call model.trainable('readout_tail') first")
+    optimizer = torch.optim.AdamW(params, cfg.SOLVER.LR, weight_decay=0)
+    schedule = lr_by_epoch(cfg)
+    ckpt_dir = os.path.join(log_dir, "checkpoints")
+    os.makedirs(ckpt_dir, exist_ok=True)
+    n_parameters = sum(p.numel() for p in params)
+    logs = []
+    for epoch in range(start_epoch, cfg.SOLVER.MAX_EPOCH):
+        for group in optimizer.param_groups:
+            group["lr"] = schedule[epoch]
+        stats = train_one_epoch(model, SalLoss(), data, optimizer, device, epoch, cfg, gamma=gamma)
+        if (epoch + 1) % save_ckpt_freq == 0 or epoch + 1 == cfg.SOLVER.MAX_EPOCH:
+            torch.save(model.state_dict(), os.path.join(ckpt_dir, "ckpt_%d.pth" % (epoch + 1)))
+        line = dict({"train_%s" % k: v for k, v in stats.items()}, epoch=epoch, n_parameters=n_parameters)
+        logs.append(line)
+        print(json.dumps(line))
+        with open(os.path.join(log_dir, "log.txt"), mode="a", encoding="utf-8") as f:
+            f.write(json.dumps(line) + "\n")
+    return logs
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    print(args)
+    check_trainable(args.trainable)
+    _single_rank()
+    if not torch.cuda.is_available():
+        raise SystemExit("mspi_amd.train needs an MI355X (no CPU fallback)")
+    import numpy as np
+    from . import engine as E
+    from . import inference as I
+    from .avsp_dataloader import AudioVisualDataset
+    torch.manual_seed(args.seed)
+    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    I.device = device
+    I._RESOLUTION[:] = args.resolution
+    model = I.build_model(args.model, args.resolution, weight=args.weights or None, use_sound=args.use_sound)
+    E.autotune(False)      # the tail is re-packed at every step: nothing to tune once
+    model.trainable(args.trainable)
+    cfg = model.cfg
+    cfg.DATA.USE_SOUND = bool(args.use_sound)
+    batch = cfg.TRAIN.BATCH_SIZE if args.batch is None else args.batch
+    data = AudioVisualDataset(args.path_data, args.dataset, args.split, args.clip_size, "train", args.use_sound,
+                              tuple(args.resolution), batch_size=batch, generator=np.random.default_rng(args.seed),
+                              workers=args.workers, device=device)
+    os.makedirs(args.log_dir, exist_ok=True)
+    return train(model, data, cfg, device, args.log_dir, args.start_epoch, args.save_ckpt_freq, args.gamma)
+
+
+if __name__ == "__main__":
+    main()
