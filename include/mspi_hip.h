@@ -685,6 +685,41 @@ int mspi_conv_wgrad_fwd(const MspiConvDesc* d, const float* x, const float* dy, 
 int mspi_upsample_bwd(const float* dy, int64_t ldy, const float* u /*NULL without ReLU*/, int64_t ldu, float* dx, int64_t ldx,
                       int32_t NT, int32_t H, int32_t W, int32_t C, int32_t factor, int32_t act, mspi_stream_t stream);
 
+/* Training kernels for the convs in front of the readout tail (csrc/readout_train.hip).  fp32; every entry point is bitwise
+ * repeatable: sums that cross a workgroup go through `ws` as per-workgroup records added (merged) in a fixed order.
+ *
+ * mspi_conv_wgrad_wide_fwd: mspi_conv_wgrad_fwd's result (dW dense [Cout][kT*kH*kW*C], db [Cout]) for wide layers: stored
+ * C and Cout multiples of 32, each at most 192, at most 27 taps, stride 1, sC == 1, input strides and ldy multiples of 4,
+ * fewer than 2^31 rows, x and dy 16-byte aligned.  A workgroup owns a (32 x 32)-channel pair with all its taps and a slice
+ * of the rows; it stages boxes of at most 128 output positions -- its columns of dy and its channels of x over the box grown
+ * by the kernel's halo -- through LDS once each, and every tap reads from there (v_mfma_f32_32x32x2_f32, rows as the
+ * contraction).  A slice is 4 boxes, 32 from 512 boxes on; a 1x1x1 kernel over dense rows takes boxes of 128 consecutive rows.
+ * mspi_conv_wgrad_wide_supported: 1 or 0 for the descriptor alone; mspi_conv_wgrad_wide_variant: boxes per slice, or -1 for
+ * exactly what the launch refuses, the reason in mspi_last_error(); mspi_conv_wgrad_wide_ws_bytes: host arithmetic, 0 for a
+ * refused descriptor.
+ *
+ * BatchNorm on batch statistics over rows [M][C], C a multiple of 4 up to 192, M >= 2 (M == 1 is refused by name, as torch
+ * refuses it); row strides multiples of 4, every pointer 16-byte aligned; ws: mspi_bn_ws_bytes(M, C) bytes.
+ * mspi_bn_stats: mean, biased variance and rstd = 1 / sqrt(var + eps) per channel.  Groups of 512 rows give (mean, M2)
+ * records from sums shifted by the group's first row; a second launch merges them left to right by Chan's formula.
+ * mspi_bn_apply: y = gamma (x - mean) rstd + beta, then ReLU when act == MSPI_ACT_RELU (MSPI_ACT_NONE otherwise).
+ * mspi_bn_bwd: dbeta = sum dy, dgamma = sum dy x^, dx = gamma rstd (dy - dbeta / M - x^ dgamma / M) with x^ = (x - mean) rstd
+ * recomputed from the pre-norm x.  y != NULL: the forward's post-ReLU output, dy counts only where y > 0.  Three launches:
+ * group sums, their ordered add, the apply. */
+int mspi_conv_wgrad_wide_supported(const MspiConvDesc* d);
+size_t mspi_conv_wgrad_wide_ws_bytes(const MspiConvDesc* d);
+int mspi_conv_wgrad_wide_variant(const MspiConvDesc* d, const void* x, const void* dy);
+int mspi_conv_wgrad_wide_fwd(const MspiConvDesc* d, const float* x, const float* dy, float* dW, float* db, void* ws,
+                             mspi_stream_t stream);
+size_t mspi_bn_ws_bytes(int64_t M, int32_t C);
+int mspi_bn_stats(const float* x, int64_t ldx, int64_t M, int32_t C, float eps, float* mean, float* var, float* rstd, void* ws,
+                  mspi_stream_t stream);
+int mspi_bn_apply(const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                  float* y, int64_t ldy, int64_t M, int32_t C, int32_t act, mspi_stream_t stream);
+int mspi_bn_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* y /*NULL without ReLU*/, int64_t ldy,
+                const float* mean, const float* rstd, const float* gamma, float* dx, int64_t lddx, float* dgamma, float* dbeta,
+                void* ws, int64_t M, int32_t C, mspi_stream_t stream);
+
 /* Bilinear resize of N maps [H][W] -> [Ho][Wo], what upstream does with cv2.resize(..., INTER_LINEAR default) when it brings
  * the prediction to the fixation map's size (utils/compute_saliency_metrics.py:119-122) and the density to the model's size
  * (avsp_dataloader.py:176).  src is uint8 (src_is_u8 != 0: a decoded image, values used as 0..255, unscaled) or float; dst is

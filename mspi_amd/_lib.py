@@ -228,6 +228,15 @@ _SIGNATURES = {
     "mspi_conv_wgrad_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
     "mspi_upsample_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, _P]),
+    "mspi_conv_wgrad_wide_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "mspi_conv_wgrad_wide_ws_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "mspi_conv_wgrad_wide_variant": (C.c_int, [C.POINTER(ConvDesc), _P, _P]),
+    "mspi_conv_wgrad_wide_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
+    "mspi_bn_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "mspi_bn_stats": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P, _P]),
+    "mspi_bn_apply": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "mspi_bn_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64,
+                              C.c_int32, _P]),
     "mspi_resize_bilinear_fwd": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mspi_resize_fixation_fwd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mspi_rowgemm_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),

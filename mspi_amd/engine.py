@@ -25,7 +25,7 @@ DEFAULT_PREC = {"f32": PREC_F32, "f16x3": PREC_F16X3}[_os.environ.get("MSPI_GEMM
 
 __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedConv", "PackedDw", "conv", "dwconv", "maxpool",
            "layernorm", "attention", "upsample", "upsample_sum", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine",
-           "se_gate", "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "se_gate", "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "conv_wgrad_wide", "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 def rup4(c):
@@ -1419,6 +1419,106 @@ def upsample_bwd(dy, factor, u=None, act=ACT_NONE):
         check(lib.mspi_upsample_bwd(dy.ptr, dy.ld, u.ptr if u is not None else None, u.ld if u is not None else 0, dx.ptr, dx.ld,
                                     dy.N * dy.T, dx.H, dx.W, dy.Cs, factor, act, _stream()), "mspi_upsample_bwd")
     return dx
+
+
+# ----------------------------------------------------------------------------- readout head training (csrc/readout_train.hip)
+WGRAD_WIDE_BOX_ROWS = 128       # output rows per staged box of mspi_conv_wgrad_wide_fwd
+WGRAD_WIDE_SLICES = (4, 32)     # boxes per slice: the codes mspi_conv_wgrad_wide_variant answers
+WGRAD_WIDE_BIG_BOXES = 512      # boxes from which the long slice is taken
+BN_ROWS = 512                   # rows per workgroup record of mspi_bn_stats / mspi_bn_bwd
+
+
+def conv_wgrad_wide_variant(x, dy, pk):
+    """The instantiation conv_wgrad_wide(x, dy, pk) launches (boxes per slice), -1 where it refuses; host only."""
+    return _lib.load().mspi_conv_wgrad_wide_variant(C.byref(_wgrad_desc(x, dy, pk)), x.ptr, dy.ptr)
+
+
+def conv_wgrad_wide(x, dy, pk):
+    """conv_wgrad for the wide layers of the readout (stored channels multiples of 32 up to 192, stride 1, <= 27 taps): every
+    operand staged through LDS once per workgroup.  Returns (dW, db) in the parameter's layout."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    if x.Cs != pk.cin_s or dy.Cs != pk.cout_s:
+        raise MspiError("conv_wgrad_wide: x has %d / dy %d stored channels, the layer %d -> %d" % (x.Cs, dy.Cs, pk.cin_s, pk.cout_s))
+    d = _wgrad_desc(x, dy, pk)
+    if not dy.dense or dy.M != x.N * d.To * d.Ho * d.Wo or dy.buf.device != x.buf.device:
+        raise MspiError("conv_wgrad_wide: dy has %d rows, the layer's output %d (or dy is not dense)"
+                        % (dy.M, x.N * d.To * d.Ho * d.Wo))
+    if lib.mspi_conv_wgrad_wide_variant(C.byref(d), x.ptr, dy.ptr) < 0:
+        raise MspiError("conv_wgrad_wide: %s" % lib.mspi_last_error().decode("utf-8", "replace"))
+    dev = x.buf.device
+    kt, kh, kw = pk.k
+    dW = torch.empty(pk.cout_s, kt, kh, kw, pk.cin_s, dtype=torch.float32, device=dev)
+    db = torch.empty(pk.cout_s, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_conv_wgrad_wide_ws_bytes(C.byref(d)) // 4, dtype=torch.float32, device=dev)   # stream-ordered
+    taps = kt * kh * kw
+    with _Timed("conv_wgrad_wide", 2.0 * dy.M * taps * pk.cin * pk.cout, 4.0 * (x.M * pk.cin + dy.M * pk.cout),
+                "M=%d K=%d(%dx%d) N=%d" % (dy.M, taps * pk.cin, taps, pk.cin, pk.cout)):
+        check(lib.mspi_conv_wgrad_wide_fwd(C.byref(d), x.ptr, dy.ptr, dW.data_ptr(), db.data_ptr(), ws.data_ptr(), _stream()),
+              "mspi_conv_wgrad_wide_fwd")
+    return dW[:pk.cout, :, :, :, :pk.cin].permute(0, 4, 1, 2, 3), db[:pk.cout]
+
+
+def _bn_rows(name, x):
+    if not x.dense or x.Cs != x.C:
+        raise MspiError("%s: rows must be dense with a channel count that is a multiple of 4" % name)
+    return x.M, x.C
+
+
+def _bn_vec(name, what, t, Cc, dev):
+    if t.dtype != torch.float32 or t.numel() != Cc or t.device != dev or not t.is_contiguous():
+        raise MspiError("%s: %s must be a contiguous fp32 [%d] tensor on %s" % (name, what, Cc, dev))
+    return t.data_ptr()
+
+
+def bn_stats(x, eps=1e-5):
+    """Per-channel batch statistics of the CL x over its M rows: (mean, biased var, rstd = 1 / sqrt(var + eps)), fp32 [C]."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    M, Cc = _bn_rows("bn_stats", x)
+    dev = x.buf.device
+    out = torch.empty(3, Cc, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_bn_ws_bytes(M, Cc) // 4, dtype=torch.float32, device=dev)                     # stream-ordered
+    with _Timed("bn_stats", 4.0 * M * Cc, 4.0 * M * Cc, "M=%d C=%d" % (M, Cc)):
+        check(lib.mspi_bn_stats(x.ptr, x.ld, M, Cc, eps, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(),
+                                _stream()), "mspi_bn_stats")
+    return out[0], out[1], out[2]
+
+
+def bn_apply(x, mean, rstd, gamma, beta, act=ACT_NONE, out=None):
+    """y = gamma (x - mean) rstd + beta, then ReLU with act == ACT_RELU; a CL like x."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    M, Cc = _bn_rows("bn_apply", x)
+    dev = x.buf.device
+    if out is None:
+        out = alloc(x.N, x.T, x.H, x.W, x.C, dev)
+    ptrs = [_bn_vec("bn_apply", n, t, Cc, dev) for n, t in (("mean", mean), ("rstd", rstd), ("gamma", gamma), ("beta", beta))]
+    with _Timed("bn_apply", 3.0 * M * Cc, 8.0 * M * Cc, "M=%d C=%d" % (M, Cc)):
+        check(lib.mspi_bn_apply(x.ptr, x.ld, ptrs[0], ptrs[1], ptrs[2], ptrs[3], out.ptr, out.ld, M, Cc, act, _stream()),
+              "mspi_bn_apply")
+    return out
+
+
+def bn_bwd(dy, x, mean, rstd, gamma, y=None):
+    """Backward of bn_apply(x, ...) on batch statistics for the output gradient dy; y: the forward's post-ReLU output when
+    it ran with ACT_RELU (the mask), None otherwise.  Returns (dx, dgamma, dbeta): a CL like x and two fp32 [C]."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    M, Cc = _bn_rows("bn_bwd", x)
+    dev = x.buf.device
+    for t in (dy, y):
+        if t is not None and ((t.M, t.C) != (M, Cc) or not t.dense or t.buf.device != dev):
+            raise MspiError("bn_bwd: dy and y must match x (%d rows x %d channels, dense)" % (M, Cc))
+    ptrs = [_bn_vec("bn_bwd", n, t, Cc, dev) for n, t in (("mean", mean), ("rstd", rstd), ("gamma", gamma))]
+    dx = alloc(x.N, x.T, x.H, x.W, x.C, dev)
+    dgb = torch.empty(2, Cc, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_bn_ws_bytes(M, Cc) // 4, dtype=torch.float32, device=dev)                     # stream-ordered
+    with _Timed("bn_bwd", 8.0 * M * Cc, 4.0 * M * Cc * (6 if y is not None else 4), "M=%d C=%d" % (M, Cc)):
+        check(lib.mspi_bn_bwd(dy.ptr, dy.ld, x.ptr, x.ld, y.ptr if y is not None else None, y.ld if y is not None else 0,
+                              ptrs[0], ptrs[1], ptrs[2], dx.ptr, dx.ld, dgb[0].data_ptr(), dgb[1].data_ptr(), ws.data_ptr(),
+                              M, Cc, _stream()), "mspi_bn_bwd")
+    return dx, dgb[0], dgb[1]
 
 
 def mean_rows(x, N, R, out):

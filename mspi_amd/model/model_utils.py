@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from .. import engine as E
 from .._lib import MspiError
-from ..autograd import ReadoutTail, pack_readout_tail, readout_tail_forward
+from ..autograd import ReadoutHead, ReadoutTail, pack_readout_tail, r0_parts, readout_tail_forward
 from ..backbones.convnext import ConvNeXtTinyFeatures
 from ..backbones.resnet import get_resnet18
 from ..module import HipModule, to_cl
@@ -443,17 +443,10 @@ class _SaliencyBase(HipModule):
             "r10": E.pack_conv(r[10].weight, r[10].bias, None, (1, 1, 1), (0, 1, 1), E.ACT_RELU),
             "r12": E.pack_conv(r[12].weight, r[12].bias, None, (1, 1, 1), (0, 1, 1), E.ACT_NONE),
             "tail_key": self._tail_key(),
+            "head_key": self._head_key(),
         }
 
-    @staticmethod
-    def _r0_parts(weight, bias):
-        """The readout's 1x1x1 conv over cat(s0', up2(s1'), up4(s2'), up8(s3)) with s0' = s0 + up2(s1') + up4(s2') + up8(s3):
-        a 1x1x1 conv commutes with a per-channel bilinear up-sample, so with W = [W0|W1|W2|W3]
-        r0(cat) = W0 s0 + b + up2((W0+W1) s1') + up4((W0+W2) s2') + up8((W0+W3) s3).  Returns [(w, b)] * 4, summed in fp32."""
-        w = weight.detach().float().flatten(1)
-        d = w.shape[1] // 4
-        w0 = w[:, :d]
-        return [(w0.contiguous(), bias.detach().float())] + [((w0 + w[:, j * d:(j + 1) * d]).contiguous(), None) for j in (1, 2, 3)]
+    _r0_parts = staticmethod(r0_parts)      # the split of readout[0] over the coarse maps (autograd.r0_parts)
 
     def _pack_r0_parts(self, conv):
         return [E.pack_conv(w, b) for w, b in self._r0_parts(conv.weight, conv.bias)]
@@ -501,6 +494,13 @@ class _SaliencyBase(HipModule):
     def _fuse_readout(self, pk, cat, s0, s1, s2, s3, masks, pm, features=False):
         """SA gating, top-down fusion and readout (model/model_utils.py:566-572); features=True stops in front of readout[8]
         and returns y4 [B,4,h,w,64]."""
+        key = pk["head_key"] if features == "maps" else self._head_key()     # "maps": ReadoutHead packs the live values itself
+        if pk["head_key"] != key:      # an optimiser step or a load has moved readout[0..5] since the four were packed
+            r = self.readout
+            pk["r0"], pk["r0_parts"] = E.pack_conv(r[0].weight, r[0].bias), self._pack_r0_parts(r[0])
+            pk["r1"] = E.pack_conv(r[1].weight, r[1].bias, r[2], (1, 1, 1), (1, 1, 1), E.ACT_RELU)
+            pk["r4"] = E.pack_conv(r[4].weight, r[4].bias, r[5], (1, 1, 1), (0, 1, 1), E.ACT_RELU)
+            pk["head_key"] = key
         self.sa_2.run(s2, masks, pm.slice(64, 32))
         E.upsample(s3, 2, dst=s2, accumulate=True)
         self.sa_1.run(s1, masks, pm.slice(32, 32))
@@ -508,6 +508,8 @@ class _SaliencyBase(HipModule):
             # r0 on the coarse maps, up-sampled after it (_r0_parts): neither s0' nor the 768-channel concat is materialised
             E.upsample_sum(s1, [(s2, 2), (s3, 4)])
             self.sa_0.run(s0, masks, pm.slice(0, 32))
+            if features == "maps":     # trainable("readout"): autograd.ReadoutHead takes over from here
+                return s0, s1, s2, s3
             p0, p1, p2, p3 = pk["r0_parts"]
             y = E.conv(s0, p0)
             E.upsample_sum(y, [(E.conv(s1, p1), 2), (E.conv(s2, p2), 4), (E.conv(s3, p3), 8)])
@@ -543,10 +545,22 @@ class _SaliencyBase(HipModule):
         # in place and keep data_ptr); an assignment `p.data = ...` need not bump it but moves data_ptr, which is why the key holds that too
         return tuple((p.data_ptr(), p._version) for i in (8, 10, 12) for p in (r[i].weight, r[i].bias))
 
+    def _head_key(self):
+        """The same for what r0, r0_parts, r1 and r4 were built from: the weights and biases of readout[0], [1], [4] and the
+        affine parameters and running statistics of the two BatchNorm layers folded into r1 and r4."""
+        r = self.readout
+        ts = [t for i in (0, 1, 4) for t in (r[i].weight, r[i].bias)]
+        ts += [t for i in (2, 5) for t in (r[i].weight, r[i].bias, r[i].running_mean, r[i].running_var)]
+        return tuple((t.data_ptr(), t._version) for t in ts)
+
     TAIL_PARAMS = tuple("readout.%d.%s" % (i, n) for i in (8, 10, 12) for n in ("weight", "bias"))
 
     def trainable(self, what):
-        """trainable("readout_tail"): the three convs readout[8], readout[10], readout[12] become trainable on top of a frozen
+        """trainable("readout"): the whole readout Sequential trains -- all 16 of its tensors get requires_grad, a forward with
+        grad enabled computes the four fused pyramid maps as in inference and hands them to autograd.ReadoutHead (readout[0],
+        [1], [4] with readout[2] and [5] on BATCH statistics, which frozen_encoder() puts in train()) and then to
+        autograd.ReadoutTail.  SA gating, the laterals, the fusion and every encoder stay frozen.
+        trainable("readout_tail"): the three convs readout[8], readout[10], readout[12] become trainable on top of a frozen
         network -- every other parameter gets requires_grad_(False), and a forward with grad enabled computes the features in
         front of readout[8] as in inference (eval BatchNorm, folded) and hands them to autograd.ReadoutTail.
         trainable(None) switches back and restores the flags found at switch-on.  Off by default."""
@@ -556,22 +570,63 @@ class _SaliencyBase(HipModule):
                 p.requires_grad_(flag)
             d["_trainable"] = None
             return self
-        if what != "readout_tail":
-            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail' is)" % (what,))
+        if what not in ("readout_tail", "readout"):
+            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail' and 'readout' are)" % (what,))
+        if what == "readout" and not DECODER_FUSED:
+            raise MspiError("trainable('readout') needs the fused decoder path: it is switched off by MSPI_DECODER_FUSED=0")
         if d.get("_trainable") is None:
             d["_trainable_saved"] = [(p, p.requires_grad) for p in self.parameters()]
         d["_trainable"] = what
         tail = set(self.TAIL_PARAMS)
         for name, p in self.named_parameters():
-            p.requires_grad_(name in tail)
+            p.requires_grad_(name.startswith("readout.") if what == "readout" else name in tail)
         return self
 
     def _training_tail(self):
-        """True when this forward goes through autograd.ReadoutTail."""
-        return self.__dict__.get("_trainable") == "readout_tail" and torch.is_grad_enabled()
+        """What _forward stops at when this forward carries a graph: True (the features y4, for autograd.ReadoutTail), "maps"
+        (the four pyramid maps, for autograd.ReadoutHead and then ReadoutTail) or False."""
+        what = self.__dict__.get("_trainable")
+        if what is None or not torch.is_grad_enabled():
+            return False
+        return "maps" if what == "readout" else True
+
+    def _check_eval(self):
+        """The forward's guard.  Under trainable("readout") exactly readout[2] and readout[5] may be in train() (they run on
+        batch statistics in autograd.ReadoutHead); any other module in train() is refused by name, as the model itself is."""
+        super()._check_eval()
+        if self.__dict__.get("_trainable") != "readout":
+            return
+        allowed = {id(self.readout[2]), id(self.readout[5])}
+        for name, mod in self.named_modules():
+            if mod.training and id(mod) not in allowed:
+                raise MspiError("%s.%s is in train() mode: under trainable('readout') only readout.2 and readout.5 run on batch "
+                                "statistics; call frozen_encoder()" % (type(self).__name__, name))
+
+    def _frozen_eval(self):
+        """frozen_encoder() under a trainable switch: eval() everywhere (folded BatchNorm), except that the readout's two
+        BatchNorm layers run on batch statistics when the whole readout trains.  True when a switch is on."""
+        what = self.__dict__.get("_trainable")
+        if what is None:
+            return False
+        self.eval()
+        if what == "readout":
+            self.readout[2].train()
+            self.readout[5].train()
+        return True
 
     def _tail_with_grad(self, y4):
         r = self.readout
+        if isinstance(y4, tuple):
+            if not (r[2].training and r[5].training):
+                # ReadoutHead normalises with BATCH statistics whatever the modules' mode; in eval() the no_grad forward of the
+                # same model folds the RUNNING statistics, so the two maps would differ silently
+                raise MspiError("trainable('readout'): a forward with grad runs readout.2 and readout.5 on batch statistics, "
+                                "but they are in eval() mode; call frozen_encoder() (engine_train.train_one_epoch does)")
+            bn = [(r[i].running_mean, r[i].running_var, r[i].num_batches_tracked) for i in (2, 5)]
+            maps = [s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4]
+            y = ReadoutHead.apply(*maps, r[0].weight, r[0].bias, r[1].weight, r[1].bias, r[2].weight, r[2].bias, r[4].weight,
+                                  r[4].bias, r[5].weight, r[5].bias, bn[0], bn[1])
+            return ReadoutTail.apply(y, r[8].weight, r[8].bias, r[10].weight, r[10].bias, r[12].weight, r[12].bias)
         y = y4.buf.view(y4.N, y4.T, y4.H, y4.W, y4.ld)
         return ReadoutTail.apply(y, r[8].weight, r[8].bias, r[10].weight, r[10].bias, r[12].weight, r[12].bias)
 
@@ -630,8 +685,7 @@ class AudioVisualSaliencyModel(_SaliencyBase):
                        cfg.MODEL.IMAGE_SALIENCY_ENCODER_WEIGHT, "image saliency encoder weights")
 
     def frozen_encoder(self):
-        if self.__dict__.get("_trainable") == "readout_tail":
-            self.eval()      # frozen means folded eval BatchNorm everywhere; the tail has neither BatchNorm nor dropout
+        if self._frozen_eval():      # frozen means folded eval BatchNorm everywhere; the tail has neither BatchNorm nor dropout
             return
         self.audnet.eval()
         self.image_encoder.eval()
@@ -662,7 +716,8 @@ class AudioVisualSaliencyModel(_SaliencyBase):
     def forward(self, clips, audios, frame_feats=None):
         """frame_feats: optional (f1 [B*T,h,w,96], f0 [B*T,h/2,w/2,320]) from encode_frames() for the clips' frames in
         (b t) order -- the image branch then starts at the adapter (sliding-window inference re-uses 15 of 16 frames).
-        After trainable("readout_tail") and with grad enabled, the map carries the graph of autograd.ReadoutTail."""
+        After trainable("readout_tail") or trainable("readout") and with grad enabled, the map carries the graph of
+        autograd.ReadoutTail (and autograd.ReadoutHead)."""
         tail = self._training_tail()
         with torch.no_grad():
             y, loss = self._forward(clips, audios, frame_feats, features=tail)
@@ -728,8 +783,7 @@ class VisualSaliencyModel(_SaliencyBase):
                        cfg.MODEL.IMAGE_SALIENCY_ENCODER_WEIGHT, "image saliency encoder weights")
 
     def frozen_encoder(self):
-        if self.__dict__.get("_trainable") == "readout_tail":
-            self.eval()
+        if self._frozen_eval():
             return
         self.image_encoder.eval()
 
