@@ -1090,7 +1090,7 @@ ATTN_PLANES = _os.environ.get("MSPI_ATTN_PLANES", "1") != "0"      # A/B switch:
 # in the hi half.  First sight of an attention LAYER (per shape) while tuning: operands beyond a quarter of that move that
 # layer's shape to the fp32 MFMA kernel for good (same contract as the GEMM packs' range check).  The decision lives in the
 # `slot` dict the module passes from its packed plan (pk["attn_prec"]), so every layer is checked on its own data and a
-# weight reload or .to() (HipModule._invalidate) checks again.  ATTN_PREC: the shape-keyed table of callers without a slot.
+# weight reload, .to() or in-place write (the plan is rebuilt: module.HipModule.pk) checks again.  ATTN_PREC: the shape-keyed table of callers without a slot.
 ATTN_PREC = {}
 LAST_ATTN = [None]      # (descriptor, has_bias, has_mask, has_tok, has_ws) of the last attention launch: attn_variant()
 

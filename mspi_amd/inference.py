@@ -334,7 +334,8 @@ class _WindowRunner:
             out = self.finish()
             if out is not None:
                 _write_maps(*out, args)
-            self.pipe = GraphPipeline(self._fn(cached), [t.to(device) for t in inputs], depth=self.depth, layouts=3)
+            self.pipe = GraphPipeline(self._fn(cached), [t.to(device) for t in inputs], depth=self.depth, layouts=3,
+                                      watch=self.model)
             self.key = key
             idle = self.pipe.prepare(2)
             idle[1].wait_stream(torch.cuda.current_stream())

@@ -475,7 +475,8 @@ class _SaliencyBase(HipModule):
         frame's features are the same in every window that contains it: cache them and pass them to
         forward(..., frame_feats=...) -- the clip loop of inference.py does."""
         self._check_eval()
-        o1, o0 = self.image_encoder.run(frames.float()[:, :, None])
+        with self.plans_checked():
+            o1, o0 = self.image_encoder.run(frames.float()[:, :, None])
         return (o1.buf.view(o1.N, o1.H, o1.W, o1.ld)[..., :o1.C], o0.buf.view(o0.N, o0.H, o0.W, o0.ld)[..., :o0.C])
 
     @staticmethod
@@ -494,13 +495,8 @@ class _SaliencyBase(HipModule):
     def _fuse_readout(self, pk, cat, s0, s1, s2, s3, masks, pm, features=False):
         """SA gating, top-down fusion and readout (model/model_utils.py:566-572); features=True stops in front of readout[8]
         and returns y4 [B,4,h,w,64]."""
-        key = pk["head_key"] if features == "maps" else self._head_key()     # "maps": ReadoutHead packs the live values itself
-        if pk["head_key"] != key:      # an optimiser step or a load has moved readout[0..5] since the four were packed
-            r = self.readout
-            pk["r0"], pk["r0_parts"] = E.pack_conv(r[0].weight, r[0].bias), self._pack_r0_parts(r[0])
-            pk["r1"] = E.pack_conv(r[1].weight, r[1].bias, r[2], (1, 1, 1), (1, 1, 1), E.ACT_RELU)
-            pk["r4"] = E.pack_conv(r[4].weight, r[4].bias, r[5], (1, 1, 1), (0, 1, 1), E.ACT_RELU)
-            pk["head_key"] = key
+        if features != "maps":         # "maps": ReadoutHead packs the live values itself
+            self._refresh_head(pk)
         self.sa_2.run(s2, masks, pm.slice(64, 32))
         E.upsample(s3, 2, dst=s2, accumulate=True)
         self.sa_1.run(s1, masks, pm.slice(32, 32))
@@ -530,13 +526,40 @@ class _SaliencyBase(HipModule):
     def _readout_tail(self, pk, y4):
         """readout[8], [10], [12] and the log-softmax on y4 [B,4,h,w,64]: four launches (autograd.readout_tail_forward; the
         trainable form of the same launches is autograd.ReadoutTail)."""
+        self._refresh_tail(pk)
+        return readout_tail_forward(y4, pk["r8"], pk["r10"], pk["r12"])[0]
+
+    # The readout trains (trainable()), so an optimiser moves it at every step: its packs follow the two keys below and are
+    # replaced one group at a time, and the plan's own key (module.HipModule.pk) leaves the readout's tensors out -- a step
+    # must not rebuild the laterals and the SA fold.
+    _PK_SELF_KEYED = ("readout",)
+
+    def _refresh_head(self, pk):
+        key = self._head_key()
+        if pk["head_key"] != key:      # an optimiser step or a load has moved readout[0..5] since the four were packed
+            r = self.readout
+            pk["r0"], pk["r0_parts"] = E.pack_conv(r[0].weight, r[0].bias), self._pack_r0_parts(r[0])
+            pk["r1"] = E.pack_conv(r[1].weight, r[1].bias, r[2], (1, 1, 1), (1, 1, 1), E.ACT_RELU)
+            pk["r4"] = E.pack_conv(r[4].weight, r[4].bias, r[5], (1, 1, 1), (0, 1, 1), E.ACT_RELU)
+            pk["head_key"] = key
+
+    def _refresh_tail(self, pk):
         key = self._tail_key()
         if pk["tail_key"] != key:      # an optimiser has moved the tail in place since the three were packed
             r = self.readout
             pk["r8"], pk["r10"], pk["r12"] = pack_readout_tail(r[8].weight, r[8].bias, r[10].weight, r[10].bias,
                                                                r[12].weight, r[12].bias)
             pk["tail_key"] = key
-        return readout_tail_forward(y4, pk["r8"], pk["r10"], pk["r12"])[0]
+
+    def _pk_refresh(self, pk):
+        """What a `pk` access outside a forward sees: the readout's packs at the present values, as the forward would make
+        them.  In a forward that carries a graph the head is left alone (ReadoutHead packs the live values itself)"""
+        grad_tail = self._training_tail()
+        with torch.no_grad():
+            if grad_tail != "maps":
+                self._refresh_head(pk)
+            if not grad_tail:          # ... and ReadoutTail does the same for the tail
+                self._refresh_tail(pk)
 
     def _tail_key(self):
         """Identity and in-place version of the six tail tensors: what the packs r8, r10, r12 were built from."""

@@ -54,10 +54,23 @@ class GraphPipeline:
     the D2H copy on the replay's stream behind the graph, both HALVE the throughput (603 -> 264..303 windows/s: 38 k posted
     PCIe writes on the graph's critical path / the copy serialising the two graphs in flight), and a `.cpu()` by the caller
     runs on the NULL stream, which drains every batch in flight.
+
+    watch: a module or an iterable of modules whose packed weights `fn` runs from.  A captured graph holds the ADDRESSES of
+    the packed buffers it was captured with, so weights that change afterwards never reach a replay.  The pipeline records
+    the identity and in-place version of every parameter and buffer below the watched modules (module.TensorWatch) in front
+    of the capture and compares them in every submit*(): after a load_state_dict, a .to() / .float(), an optimiser step or
+    any other in-place write to one of them -- on the module itself, a sub-module or a plain container below it -- the
+    submit raises RuntimeError and a new pipeline has to be built.  Not seen: a tensor that is neither a registered
+    parameter nor a buffer, and switches read from the environment.  The comparison is two list comparisons over the
+    tensors (about 0.3 ms of host time for the x3dl model's 1,500).  None (default): nothing is compared.
     """
 
-    def __init__(self, fn, example_inputs, depth=2, layouts=1, log=None, capture_error_mode="thread_local"):
+    def __init__(self, fn, example_inputs, depth=2, layouts=1, log=None, capture_error_mode="thread_local", watch=None):
         self.fn, self.depth = fn, max(1, int(depth))
+        self._watch = None
+        if watch is not None:
+            from .module import TensorWatch
+            self._watch = TensorWatch((watch,) if isinstance(watch, torch.nn.Module) else tuple(watch))
         self._copy_stream = None
         self.example = tuple(example_inputs)
         if not all(torch.is_tensor(t) and t.is_cuda for t in self.example):
@@ -126,7 +139,14 @@ class GraphPipeline:
         return n / (time.perf_counter() - t0)
 
     # ------------------------------------------------------------------ steady state
+    def _check_watch(self):
+        if self._watch is not None and not self._watch.same():
+            raise RuntimeError("GraphPipeline: a parameter or buffer of the watched model changed after the capture "
+                               "(load_state_dict, .to(), an optimiser step or another in-place write): the captured graphs "
+                               "still read the weights packed from the old values -- build a new GraphPipeline")
+
     def submit(self, *inputs):
+        self._check_watch()
         k = self._count % self.depth
         self._count += 1
         s = self.slots[k]
@@ -162,6 +182,7 @@ class GraphPipeline:
         STREAM, directly in front of the replay: the whole batch -- input assembly, forward, post-processing -- is one stream
         with no cross-stream hand-over and no allocation outside that stream's pool.  The tensors `build` reads must be
         complete (produced on this stream earlier, or synchronised by the caller)."""
+        self._check_watch()
         k = self._count % self.depth
         self._count += 1
         s = self.slots[k]

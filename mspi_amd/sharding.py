@@ -28,8 +28,8 @@ def broadcast_weights(module, src=0):
             t.copy_(flat[off:off + t.numel()].view_as(t))
             off += t.numel()
     if hasattr(module, "_invalidate"):
-        module._invalidate()        # packed weights are stale now
-    return flat.numel()
+        module._invalidate()        # frees the packs below `module` now.  Not what correctness rests on: the in-place writes
+    return flat.numel()             # moved the tensors' versions, so every plan that read them, an ancestor's included, is rebuilt
 
 
 def gather_maps(local_maps, n_total, dst=0):
