@@ -3,13 +3,13 @@
 * `CL`   -- a channels-last activation: M = N*T*H*W rows x C columns, row stride `ld`
             (floats, multiple of 4) inside a flat fp32 torch buffer.  Slicing channels is free,
             which is how concats are eliminated (producers write into their slice).
-* pack_* -- weight packing done once per parameter version: eval-mode BatchNorm folded into
-            the conv, taps made channel-minor, channel counts padded to a multiple of 4.
+* pack_* -- weight packing, done once per parameter version: packs.py, whose names are re-exported here.
 * op wrappers -- conv / dwconv / layernorm / ... : fill the POD descriptor, pass raw device
             pointers and torch's current hipStream_t.  No CPU fallback anywhere.
 """
 import ctypes as C
-import math
+import os as _os
+from functools import partial
 
 import numpy as np
 import torch
@@ -17,19 +17,15 @@ import torch
 from . import _lib
 from ._lib import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SWISH, PREC_F16X3, PREC_F32, AttnDesc, ConvDesc,
                    DwConvDesc, MspiError, MvitAugDesc, check)
-
-# GEMM arithmetic for every dense conv / Linear: "f16x3" (default; fp32-accurate split product on the f16 matrix
-# pipe, see include/mspi_hip.h) or "f32" (v_mfma_f32_32x32x2_f32).  Read when weights are packed.
-import os as _os
-DEFAULT_PREC = {"f32": PREC_F32, "f16x3": PREC_F16X3}[_os.environ.get("MSPI_GEMM_PREC", "f16x3")]
+from .packs import (DEFAULT_PREC, SP_ENABLED, PackedConv, PackedDw, PackedMlp, PackedX3dAb, PackedX3dCa, PackedX3dStem,
+                    _pack_rowgemm, _pad_vec, fold_bn, mlp_supported, pack_conv, pack_dwconv, pack_mlp, pack_mlp_tail,
+                    pack_x3d_ab, pack_x3d_ab_s2, pack_x3d_ca, pack_x3d_stem, rowgemm_ksb, rowgemm_supported, rup4,
+                    sp_supported, sp_weights, x3d_ca_supported)
 
 __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedConv", "PackedDw", "conv", "dwconv", "maxpool",
-           "layernorm", "attention", "upsample", "upsample_sum", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine",
-           "se_gate", "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "conv_wgrad_wide", "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
-
-
-def rup4(c):
-    return (c + 3) // 4 * 4
+           "layernorm", "attention", "upsample", "upsample_sum", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine", "se_gate",
+           "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "conv_wgrad_wide",
+           "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 # ----------------------------------------------------------------------------- conv autotuning
@@ -93,6 +89,17 @@ def _tune_conv(launch, key, candidates):
         import sys
         print("[tune] %s -> %d  %s" % (key, best, " ".join("%d:%.4f" % tt for tt in times)), file=sys.stderr)
     return best
+
+
+def _choose(key, tile, default, candidates, launch, *call):
+    """The kernel choice of one call: the forced `tile`; else, while autotuning, what the cache holds for `key` or, on first
+    sight, the fastest of candidates(*call) (timed now and cached); else what the cache holds; else `default`."""
+    if tile is not None:
+        return tile
+    choice = AUTOTUNE["cache"].get(key)
+    if choice is None and AUTOTUNE["on"] and not torch.cuda.is_current_stream_capturing():
+        return _tune_conv(launch, key, candidates(*call))
+    return default if choice is None else choice
 
 
 # ----------------------------------------------------------------------------- per-launch timing
@@ -266,9 +273,6 @@ def alloc(N, T, H, W, Cc, device, ld=None):
     return CL(buf, 0, N, T, H, W, Cc, ld)
 
 
-SP_ENABLED = _os.environ.get("MSPI_PRESPLIT", "1") != "0"   # A/B switch: pre-split activations between LN / GEMM / GEMM
-
-
 class SP:
     """Pre-split activation rows: two f16 planes (hi, lo) in one buffer -- what a producer's epilogue hands to the f16x3 GEMM so
     that neither operand needs conversion work in the loop (include/mspi_hip.h, mspi_gemm_sp_fwd).  Each plane is BLOCKED:
@@ -290,11 +294,6 @@ class SP:
     @property
     def ptr(self):
         return self.buf.data_ptr()
-
-
-def sp_supported(c):
-    """Channel counts the pre-split GEMM takes as its K: multiples of the 32-deep stage (then ldw == K)."""
-    return SP_ENABLED and DEFAULT_PREC == PREC_F16X3 and c % 32 == 0
 
 
 def alloc_sp(N, T, H, W, Cc, device):
@@ -320,164 +319,6 @@ def from_rows(t2d):
     return CL(t2d, 0, t2d.shape[0], 1, 1, 1, t2d.shape[1], t2d.stride(0))
 
 
-# ----------------------------------------------------------------------------- packing
-def fold_bn(weight, bias, bn):
-    """Fold an eval-mode BatchNorm (running stats) into the preceding conv: returns (w, b)."""
-    w = weight.detach().float()
-    b = None if bias is None else bias.detach().float()
-    if bn is not None:
-        s = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-        w = w * s.view(-1, *([1] * (w.dim() - 1)))
-        b0 = bn.bias.detach().float() - bn.running_mean.detach().float() * s
-        b = b0 if b is None else b0 + b * s
-    return w, b
-
-
-class PackedConv:
-    __slots__ = ("w", "bias", "k", "stride", "pad", "cin", "cin_s", "cout", "cout_s", "ldw", "act", "prec", "w_scale", "thin",
-                 "w32", "ldw32", "checked", "wsp")
-
-
-def pack_conv(weight, bias=None, bn=None, stride=(1, 1, 1), pad=(0, 0, 0), act=ACT_NONE, cin_stored=None,
-              out_scale=None, device=None, prec=None):
-    """weight: [Co,Ci] (Linear), [Co,Ci,kh,kw] (2-D) or [Co,Ci,kt,kh,kw].  Result rows are
-    [Co_s][ldw] with k = (kt,kh,kw,ci) ci fastest, Ci padded to cin_stored, Co to a multiple of 4."""
-    w, b = fold_bn(weight, bias, bn)
-    if w.dim() == 2:
-        w = w[:, :, None, None, None]
-    elif w.dim() == 4:
-        w = w[:, :, None]
-    if out_scale is not None:  # e.g. ConvNeXt layer-scale gamma folded into the producing conv
-        s = out_scale.detach().float().view(-1)
-        w = w * s.view(-1, 1, 1, 1, 1)
-        b = None if b is None else b * s
-    co, ci, kt, kh, kw = w.shape
-    cin_s = ci if cin_stored is None else cin_stored
-    assert cin_s >= ci
-    cout_s = rup4(co) if co > 1 else 1
-    K = kt * kh * kw * cin_s
-    prec = DEFAULT_PREC if prec is None else prec
-    ldw = rup4(K) if prec == PREC_F32 else (K + 31) // 32 * 32
-    wp = torch.zeros(cout_s, kt, kh, kw, cin_s, dtype=torch.float32, device=w.device)
-    wp[:co, :, :, :, :ci] = w.permute(0, 2, 3, 4, 1)
-    wf = torch.zeros(cout_s, ldw, dtype=torch.float32, device=w.device)
-    wf[:, :K] = wp.reshape(cout_s, K)
-    p = PackedConv()
-    p.thin = None
-    p.wsp = None
-    p.checked = False
-    dev = w.device if device is None else device
-    p.prec, p.w_scale = prec, 1.0
-    if prec == PREC_F16X3:
-        # power-of-two pre-scale puts max|w| in [2^13, 2^14): the lo halves of typical weights are normal f16
-        mx = float(wf.abs().max())
-        if not math.isfinite(mx):
-            raise MspiError("pack_conv: non-finite weights")
-        e = 0 if mx == 0.0 else max(-10, min(24, int(math.floor(math.log2(16384.0 / mx)))))
-        p.w_scale = float(2.0 ** e)
-        ws = wf * p.w_scale
-        hi = ws.to(torch.float16)
-        lo = (ws - hi.float()).to(torch.float16)
-        p.w = torch.stack([hi, lo]).to(dev).contiguous()
-        p.ldw32 = rup4(K)                                   # the fp32 form, for layers the range check moves off f16x3
-        p.w32 = wf[:, :p.ldw32].to(dev).contiguous()
-        if (kt, kh, kw) == (1, 1, 1) and tuple(stride) == (1, 1, 1) and tuple(pad) == (0, 0, 0):
-            p.thin = _pack_rowgemm(ws[:, :K], cin_s, cout_s, dev)
-    else:
-        p.w = wf.to(dev).contiguous()
-        p.w32, p.ldw32 = p.w, ldw
-    if b is None:
-        p.bias = None
-    else:
-        bp = torch.zeros(cout_s, dtype=torch.float32, device=w.device)
-        bp[:co] = b
-        p.bias = bp.to(dev)
-    p.k, p.stride, p.pad = (kt, kh, kw), tuple(stride), tuple(pad)
-    p.cin, p.cin_s, p.cout, p.cout_s, p.ldw, p.act = ci, cin_s, co, cout_s, ldw, act
-    return p
-
-
-def rowgemm_ksb(k):
-    """k-steps of 16 the row-stationary thin GEMM keeps in registers for K stored input columns (0: not covered)."""
-    return 2 if k <= 32 else 4 if k <= 64 else 8 if k <= 128 else 14 if k <= 224 else 0
-
-
-def rowgemm_supported(k, n):
-    """Mirror of mspi_rowgemm_supported."""
-    return bool(rowgemm_ksb(k)) and 4 <= n <= 1024
-
-
-def _pack_rowgemm(ws, k_s, n_s, dev):
-    """Scaled weights ws [n_s, k_s] -> fragment-order f16 hi/lo planes for mspi_rowgemm_fwd (layout: include/mspi_hip.h);
-    None when the shape is outside the kernel's range."""
-    if not rowgemm_supported(k_s, n_s):
-        return None
-    ksb, nch = rowgemm_ksb(k_s), (n_s + 31) // 32
-    wp = torch.zeros(nch * 32, ksb * 16, dtype=torch.float32)
-    wp[:n_s, :k_s] = ws.cpu()
-    hi = wp.to(torch.float16)
-    lo = (wp - hi.float()).to(torch.float16)
-    planes = [pl.view(nch, 32, ksb, 2, 8).permute(0, 2, 3, 1, 4).reshape(nch, ksb, 64, 8) for pl in (hi, lo)]
-    return torch.stack(planes, 2).contiguous().to(dev)      # [nch, ksb, plane, lane, 8]
-
-
-class PackedMlp:
-    __slots__ = ("w", "b1", "b2", "c", "hidden", "s1", "s2", "act", "src", "checked", "fallback")
-
-
-def _f16_scale(w):
-    mx = float(w.abs().max())
-    if not math.isfinite(mx):
-        raise MspiError("pack: non-finite weights")
-    e = 0 if mx == 0.0 else max(-10, min(24, int(math.floor(math.log2(16384.0 / mx)))))
-    return float(2.0 ** e)
-
-
-def mlp_supported(c, hidden):
-    """Shapes mspi_mlp_fwd covers (the rows stay in registers as MFMA fragments: C <= 192)."""
-    if _os.environ.get("MSPI_MLP_FUSED", "1") == "0":   # A/B switch
-        return False
-    return DEFAULT_PREC == PREC_F16X3 and c in (96, 192) and hidden % 32 == 0 and hidden <= 1024
-
-
-def pack_mlp(fc1_w, fc1_b, fc2_w, fc2_b, out_scale=None, act=ACT_GELU, device=None):
-    """Fragment-order f16 hi/lo packing of a Linear(C, hidden) -> act -> Linear(hidden, C) pair for mspi_mlp_fwd
-    (layout: include/mspi_hip.h).  out_scale (ConvNeXt layer-scale gamma) is folded into the second layer."""
-    w1 = fc1_w.detach().float().cpu()
-    w2 = fc2_w.detach().float().cpu()
-    b2 = fc2_b.detach().float().cpu()
-    if out_scale is not None:
-        g = out_scale.detach().float().cpu().view(-1)
-        w2, b2 = w2 * g[:, None], b2 * g
-    hidden, c = w1.shape
-    if w2.shape != (c, hidden) or c % 32 or hidden % 32:
-        raise MspiError("pack_mlp: shapes %s / %s" % (tuple(w1.shape), tuple(w2.shape)))
-    nch, ks, ct = hidden // 32, c // 16, c // 32
-    p = PackedMlp()
-    p.s1, p.s2 = _f16_scale(w1), _f16_scale(w2)
-
-    def planes(w, s):
-        ws = w * s
-        hi = ws.to(torch.float16)
-        return hi, (ws - hi.float()).to(torch.float16)
-
-    parts1, parts2 = [], []
-    for pl in planes(w1, p.s1):   # [hidden, C] -> [nch, n32, ks, g2, e8] -> [nch, ks, (g, n) = lane, e]
-        parts1.append(pl.view(nch, 32, ks, 2, 8).permute(0, 2, 3, 1, 4).reshape(nch, ks, 64, 8))
-    for pl in planes(w2, p.s2):   # [C, hidden] -> [ct, c32, nch, s2, eh2, g2, r4] -> [nch, s, ct, (g, c) = lane, (eh, r) = e]
-        parts2.append(pl.view(ct, 32, nch, 2, 2, 2, 4).permute(2, 3, 0, 5, 1, 4, 6).reshape(nch, 2, ct, 64, 8))
-    w1p = torch.stack(parts1, 2).reshape(nch, -1)      # [nch, ks, plane, 64, 8]
-    w2p = torch.stack(parts2, 3).reshape(nch, -1)      # [nch, s, ct, plane, 64, 8]
-    dev = fc1_w.device if device is None else device
-    p.w = torch.cat([w1p, w2p], 1).contiguous().to(dev)
-    p.b1 = fc1_b.detach().float().contiguous().to(dev)
-    p.b2 = b2.contiguous().to(dev)
-    p.c, p.hidden, p.act = c, hidden, act
-    # first-sight range check (mlp()): the layer pair as two GEMM packs, built from these when the check needs them
-    p.src, p.checked, p.fallback = (fc1_w, fc1_b, fc2_w, fc2_b, out_scale), False, None
-    return p
-
-
 def _tuning():
     return AUTOTUNE["on"] and RANGE_CHECK["on"] and DEFAULT_PREC == PREC_F16X3 and not torch.cuda.is_current_stream_capturing()
 
@@ -490,149 +331,61 @@ def range_check_input(pk, x):
     return pk.prec == PREC_F16X3
 
 
-class PackedDw:
-    __slots__ = ("w", "bias", "k", "stride", "pad", "c", "c_s", "act")
-
-
-def pack_dwconv(weight, bias=None, bn=None, stride=(1, 1, 1), pad=(0, 0, 0), act=ACT_NONE, device=None):
-    """weight: [C,1,kt,kh,kw] or [C,1,kh,kw] depthwise.  Packed as [taps][C_s]."""
-    w, b = fold_bn(weight, bias, bn)
-    if w.dim() == 4:
-        w = w[:, :, None]
-    c, one, kt, kh, kw = w.shape
-    assert one == 1
-    c_s = rup4(c)
-    wp = torch.zeros(kt * kh * kw, c_s, dtype=torch.float32, device=w.device)
-    wp[:, :c] = w.reshape(c, kt * kh * kw).t()
-    bp = torch.zeros(c_s, dtype=torch.float32, device=w.device)
-    if b is not None:
-        bp[:c] = b
-    p = PackedDw()
-    dev = w.device if device is None else device
-    p.w, p.bias = wp.to(dev).contiguous(), bp.to(dev)
-    p.k, p.stride, p.pad, p.c, p.c_s, p.act = (kt, kh, kw), tuple(stride), tuple(pad), c, c_s, act
-    return p
-
-
-class PackedX3dAb:
-    __slots__ = ("wa", "ba", "wb", "bb", "wa_scale", "cin_s", "cmid", "cmid_s")
-
-
-def pack_x3d_ab(pa, pb):
-    """Operands of the fused X3D `a` + `b` kernel (mspi_x3d_ab_fwd) from the packed 1x1x1 conv `pa` (PackedConv, f16x3: BN
-    folded, scaled hi/lo planes) and the packed 3x3x3 depthwise conv `pb` (PackedDw); None when the layer pair is outside
-    the kernel's range.  Fragment order of wa: include/mspi_hip.h."""
-    if pa.prec != PREC_F16X3 or pa.k != (1, 1, 1) or pa.stride != (1, 1, 1) or pb.k != (3, 3, 3) or pb.stride != (1, 1, 1) \
-            or pb.pad != (1, 1, 1) or pa.cout_s != pb.c_s or pa.cin_s % 8 or pa.act != ACT_RELU or pa.bias is None:
-        return None
-    ks = (pa.cin_s + 31) // 32
-    if ks not in (1, 2, 3, 6):
-        return None
-    nch = (pa.cout_s + 31) // 32
-    dev = pa.w.device
-    ws = torch.zeros(nch * 32, ks * 32, dtype=torch.float32)
-    ws[:pa.cout_s, :pa.cin_s] = (pa.w[0].float() + pa.w[1].float()).cpu()[:, :pa.cin_s]     # hi + lo = the scaled fp32 weight's 22 bits
-    hi = ws.to(torch.float16)
-    lo = (ws - hi.float()).to(torch.float16)
-    planes = [pl.view(nch, 2, 16, ks, 4, 8).permute(0, 3, 1, 4, 2, 5).reshape(nch, ks, 2, 64, 8) for pl in (hi, lo)]
-    p = PackedX3dAb()
-    p.wa = torch.stack(planes, 3).contiguous().to(dev)        # [nch, ks, half, plane, lane, 8]
-    p.ba, p.wb, p.bb = pa.bias, pb.w, pb.bias
-    p.wa_scale, p.cin_s, p.cmid, p.cmid_s = pa.w_scale, pa.cin_s, pb.c, pb.c_s
-    return p
-
-
-def _x3d_ab_desc(x, pk, out_ld, act):
-    d = _lib.X3dAbDesc()
+def _x3d_ab_desc(x, pk, out_ld, act, cls=_lib.X3dAbDesc):
+    d = cls()
     d.N, d.T, d.H, d.W = x.N, x.T, x.H, x.W
     d.Cin, d.Cmid, d.ldx, d.ldu, d.act, d.wa_scale = pk.cin_s, pk.cmid_s, x.ld, out_ld, act, pk.wa_scale
     return d
+
+
+_x3d_ab_s2_desc = partial(_x3d_ab_desc, cls=_lib.X3dAbS2Desc)
 
 
 def x3d_ab_supported(x, pk):
     return pk is not None and x.dense and x.Cs == pk.cin_s and bool(_lib.load().mspi_x3d_ab_supported(C.byref(_x3d_ab_desc(x, pk, pk.cmid_s, ACT_NONE))))
 
 
+def x3d_ab_s2_supported(x, pk):
+    return pk is not None and x.dense and x.Cs == pk.cin_s and bool(_lib.load().mspi_x3d_ab_s2_supported(C.byref(_x3d_ab_s2_desc(x, pk, pk.cmid_s, ACT_NONE))))
+
+
+# what differs between the two strides of `b`: (stride, descriptor class, Profiler names, entry point's name)
+_AB = (1, _lib.X3dAbDesc, "x3d_ab", "x3d_ab_pool", "mspi_x3d_ab_fwd")
+_AB_S2 = (2, _lib.X3dAbS2Desc, "x3d_ab_s2", "x3d_ab_s2_pool", "mspi_x3d_ab_s2_fwd")
+
+
+def _x3d_ab(rec, fwd, pool_rows, x, pk, pool, out):
+    """The fused a + b pair of record `rec`, launched by the library's `fwd` / `pool_rows` of that stride."""
+    s, desc, name, pooled, entry = rec
+    _need_gpu(x.buf)
+    if out is None:
+        out = alloc(x.N, x.T, x.H // s, x.W // s, pk.cmid, x.buf.device)
+    elif (out.N, out.T, out.H, out.W, out.Cs) != (x.N, x.T, x.H // s, x.W // s, pk.cmid_s) or not out.dense:
+        raise MspiError("%s: the output tensor does not match the layer" % name)
+    d = _x3d_ab_desc(x, pk, out.ld, ACT_NONE if pool else ACT_SWISH, desc)
+    part = torch.empty(x.N, pool_rows(C.byref(d)), pk.cmid_s, dtype=torch.float32, device=x.buf.device) if pool else None
+    # integer-valued doubles, exact: with out.M == x.M (stride 1) these are 2 M (Cin + 27) Cmid and 4 M (C + Cmid) to the bit
+    with _Timed(pooled if pool else name, 2.0 * x.M * pk.cin_s * pk.cmid + 2.0 * out.M * 27 * pk.cmid,
+                4.0 * (x.M * x.C + out.M * pk.cmid), "in=%s Cin=%d Cmid=%d" % ((x.N, x.T, x.H, x.W), x.C, pk.cmid)):
+        check(fwd(C.byref(d), x.ptr, pk.wa.data_ptr(), pk.ba.data_ptr(), pk.wb.data_ptr(), pk.bb.data_ptr(), out.ptr,
+                  part.data_ptr() if pool else None, _stream()), entry)
+    return (out, part) if pool else out
+
+
 def x3d_ab(x, pk, pool=False):
     """u = act(b_bn(dw3x3x3(relu(a_bn(a(x)))))) in one launch (csrc/x3d_block.hip); pool=True: no activation, also returns
     the [N, rows, C] partial sums of u for the squeeze-excite gate (X3DTransform with SE); otherwise act = Swish."""
     lib = _lib.load()
-    _need_gpu(x.buf)
-    out = alloc(x.N, x.T, x.H, x.W, pk.cmid, x.buf.device)
-    d = _x3d_ab_desc(x, pk, out.ld, ACT_NONE if pool else ACT_SWISH)
-    part = None
-    if pool:
-        rows = lib.mspi_x3d_ab_pool_rows(C.byref(d))
-        part = torch.empty(x.N, rows, pk.cmid_s, dtype=torch.float32, device=x.buf.device)
-    with _Timed("x3d_ab_pool" if pool else "x3d_ab", 2.0 * x.M * (pk.cin_s + 27) * pk.cmid, 4.0 * x.M * (x.C + pk.cmid),
-                "in=%s Cin=%d Cmid=%d" % ((x.N, x.T, x.H, x.W), x.C, pk.cmid)):
-        check(lib.mspi_x3d_ab_fwd(C.byref(d), x.ptr, pk.wa.data_ptr(), pk.ba.data_ptr(), pk.wb.data_ptr(), pk.bb.data_ptr(),
-                                  out.ptr, part.data_ptr() if pool else None, _stream()), "mspi_x3d_ab_fwd")
-    return (out, part) if pool else out
-
-
-def pack_x3d_ab_s2(pa, pb):
-    """Operands of the stride-2 fused X3D `a` + `b` kernel (mspi_x3d_ab_s2_fwd, the first block of a stage): the same pack as
-    pack_x3d_ab, from a depthwise conv `pb` with stride (1,2,2); None when the layer pair is outside the kernel's range."""
-    if pb.stride != (1, 2, 2) or (pa.cin_s + 31) // 32 > 3:
-        return None
-    s1 = PackedDw()
-    for f in PackedDw.__slots__:
-        setattr(s1, f, getattr(pb, f))
-    s1.stride = (1, 1, 1)
-    return pack_x3d_ab(pa, s1)
-
-
-def _x3d_ab_s2_desc(x, pk, out_ld, act):
-    d = _lib.X3dAbS2Desc()
-    d.N, d.T, d.H, d.W = x.N, x.T, x.H, x.W
-    d.Cin, d.Cmid, d.ldx, d.ldu, d.act, d.wa_scale = pk.cin_s, pk.cmid_s, x.ld, out_ld, act, pk.wa_scale
-    return d
-
-
-def x3d_ab_s2_supported(x, pk):
-    return pk is not None and x.dense and x.Cs == pk.cin_s \
-        and bool(_lib.load().mspi_x3d_ab_s2_supported(C.byref(_x3d_ab_s2_desc(x, pk, pk.cmid_s, ACT_NONE))))
+    return _x3d_ab(_AB, lib.mspi_x3d_ab_fwd, lib.mspi_x3d_ab_pool_rows, x, pk, pool, None)
 
 
 def x3d_ab_s2(x, pk, pool=False, out=None):
     """u = act(b_bn(dw3x3x3 stride (1,2,2)(relu(a_bn(a(x)))))) in one launch (csrc/x3d_head.hip); pool=True: no activation,
     also returns the [N, rows, C] partial sums of u for the squeeze-excite gate; otherwise act = Swish."""
     lib = _lib.load()
-    _need_gpu(x.buf)
     if not x3d_ab_s2_supported(x, pk):
         raise MspiError("x3d_ab_s2: input %s with %d channels is outside the fused kernel's range" % ((x.N, x.T, x.H, x.W), x.C))
-    if out is None:
-        out = alloc(x.N, x.T, x.H // 2, x.W // 2, pk.cmid, x.buf.device)
-    elif (out.N, out.T, out.H, out.W, out.Cs) != (x.N, x.T, x.H // 2, x.W // 2, pk.cmid_s) or not out.dense:
-        raise MspiError("x3d_ab_s2: the output tensor does not match the layer")
-    d = _x3d_ab_s2_desc(x, pk, out.ld, ACT_NONE if pool else ACT_SWISH)
-    part = None
-    if pool:
-        rows = lib.mspi_x3d_ab_s2_pool_rows(C.byref(d))
-        part = torch.empty(x.N, rows, pk.cmid_s, dtype=torch.float32, device=x.buf.device)
-    with _Timed("x3d_ab_s2_pool" if pool else "x3d_ab_s2", 2.0 * x.M * pk.cin_s * pk.cmid + 2.0 * out.M * 27 * pk.cmid,
-                4.0 * (x.M * x.C + out.M * pk.cmid), "in=%s Cin=%d Cmid=%d" % ((x.N, x.T, x.H, x.W), x.C, pk.cmid)):
-        check(lib.mspi_x3d_ab_s2_fwd(C.byref(d), x.ptr, pk.wa.data_ptr(), pk.ba.data_ptr(), pk.wb.data_ptr(), pk.bb.data_ptr(),
-                                     out.ptr, part.data_ptr() if pool else None, _stream()), "mspi_x3d_ab_s2_fwd")
-    return (out, part) if pool else out
-
-
-class PackedX3dStem:
-    __slots__ = ("wxy", "wt", "bias")
-
-
-def pack_x3d_stem(w_xy, w_t, bn):
-    """Operands of the fused X3D stem (mspi_x3d_stem_fwd): conv_xy's weight [24,3,1,3,3] (no bias) and the temporal depthwise
-    weight [24,1,5,1,1] with `bn` folded, as HOST arrays (they travel as kernel arguments); None for any other stem."""
-    if tuple(w_xy.shape) != (24, 3, 1, 3, 3) or tuple(w_t.shape) != (24, 1, 5, 1, 1):
-        return None
-    wt, b = fold_bn(w_t, None, bn)
-    p = PackedX3dStem()
-    p.wxy = w_xy.detach().float().cpu().reshape(24, 27).t().contiguous()      # [(ci,kh,kw)][c]
-    p.wt = wt.detach().float().cpu().reshape(24, 5).t().contiguous()          # [kt][c]
-    p.bias = (b if b is not None else torch.zeros(24)).detach().float().cpu().contiguous()
-    return p
+    return _x3d_ab(_AB_S2, lib.mspi_x3d_ab_s2_fwd, lib.mspi_x3d_ab_s2_pool_rows, x, pk, pool, out)
 
 
 def _x3d_stem_desc(x, ldy):
@@ -668,44 +421,6 @@ def x3d_stem(x, pk, out=None):
     return out
 
 
-class PackedX3dCa:
-    __slots__ = ("w", "bc", "ba", "d", "cx", "cx_s", "d_s", "wc_scale", "wa_scale")
-
-
-def x3d_ca_supported(d_s, cx_s):
-    """Mirror of mspi_x3d_ca_supported."""
-    return 4 <= d_s <= 224 and d_s % 4 == 0 and 4 <= cx_s <= 256 and cx_s % 4 == 0
-
-
-def pack_x3d_ca(pc, pa):
-    """Operands of the fused X3D block seam (mspi_x3d_ca_fwd): this block's `c` conv `pc` and the next block's `a` conv `pa`
-    (both PackedConv, 1x1x1, f16x3, ReLU); None when the pair is outside the kernel's range."""
-    ok = all(q.prec == PREC_F16X3 and q.k == (1, 1, 1) and q.stride == (1, 1, 1) and q.pad == (0, 0, 0) and q.act == ACT_RELU
-             and q.bias is not None for q in (pc, pa))
-    if not ok or pc.cout_s != pa.cin_s or pc.cin_s != pa.cout_s or not x3d_ca_supported(pc.cin_s, pc.cout_s):
-        return None
-    d_s, cx_s = pc.cin_s, pc.cout_s
-    c = 128 if d_s <= 128 else 224
-    hid = (cx_s + 31) // 32 * 32
-    nch, ks, ct = hid // 32, c // 16, c // 32
-    w1 = torch.zeros(hid, c, dtype=torch.float32)
-    w1[:cx_s, :d_s] = (pc.w[0].float() + pc.w[1].float()).cpu()[:, :d_s]      # hi + lo = the scaled fp32 weight's 22 bits
-    w2 = torch.zeros(c, hid, dtype=torch.float32)
-    w2[:d_s, :cx_s] = (pa.w[0].float() + pa.w[1].float()).cpu()[:, :cx_s]
-
-    def planes(ws):
-        hi = ws.to(torch.float16)
-        return hi, (ws - hi.float()).to(torch.float16)
-
-    parts1 = [pl.view(nch, 32, ks, 2, 8).permute(0, 2, 3, 1, 4).reshape(nch, ks, 64, 8) for pl in planes(w1)]
-    parts2 = [pl.view(ct, 32, nch, 2, 2, 2, 4).permute(2, 3, 0, 5, 1, 4, 6).reshape(nch, 2, ct, 64, 8) for pl in planes(w2)]
-    p = PackedX3dCa()
-    p.w = torch.cat([torch.stack(parts1, 2).reshape(nch, -1), torch.stack(parts2, 3).reshape(nch, -1)], 1).contiguous().to(pc.w.device)
-    p.bc, p.ba = pc.bias, pa.bias
-    p.d, p.d_s, p.cx, p.cx_s, p.wc_scale, p.wa_scale = pc.cin, d_s, pc.cout, cx_s, pc.w_scale, pa.w_scale
-    return p
-
-
 def x3d_ca(u, pk, res, gate=None):
     """(y, t) = (relu(c(u') + res), relu(a_next(y))) in one launch (csrc/mlp_fused.hip); u' = swish(u * gate) with a gate."""
     lib = _lib.load()
@@ -727,12 +442,6 @@ def x3d_ca(u, pk, res, gate=None):
     return y, t
 
 
-def _pad_vec(v, n):
-    out = torch.zeros(n, dtype=torch.float32, device=v.device)
-    out[: v.numel()] = v.detach().float().view(-1)
-    return out
-
-
 # ----------------------------------------------------------------------------- op wrappers
 def _out_extent(T, H, W, k, s, p):
     return ((T + 2 * p[0] - k[0]) // s[0] + 1, (H + 2 * p[1] - k[1]) // s[1] + 1, (W + 2 * p[2] - k[2]) // s[2] + 1)
@@ -745,16 +454,8 @@ SP_TILES = (6, 7, 9, 10, 11, 12, 13, 14)
 W_BLOCKED = _os.environ.get("MSPI_W_BLOCKED", "1") != "0"      # A/B switch: blocked weights for the LDS-DMA kernels on fp32 activations
 
 
-def sp_weights(pk):
-    """The weights of an f16x3 pack in the form mspi_gemm_sp_fwd takes: blocked like the activation planes (16 rows x 32 k =
-    1 KB contiguous, k-fastest, rows zero-padded to a multiple of 16), so that every LDS-DMA piece of a stage is 8 full cache
-    lines.  Built on first use, kept on the pack."""
-    if pk.wsp is None:
-        npad = (pk.cout_s + 15) // 16 * 16
-        w = torch.zeros(2, npad, pk.ldw, dtype=torch.float16, device=pk.w.device)
-        w[:, : pk.cout_s] = pk.w
-        pk.wsp = w.view(2, npad // 16, 16, pk.ldw // 32, 32).permute(0, 1, 3, 2, 4).contiguous()
-    return pk.wsp
+def _sp_tiles(M):
+    return [t for t in SP_TILES if t < 12 or M >= 4096]
 
 
 def _conv_sp(x, pk, out, res, act, tile, sp_out):
@@ -796,16 +497,7 @@ def _conv_sp(x, pk, out, res, act, tile, sp_out):
         d.tile = t
         return lib.mspi_gemm_sp_fwd(C.byref(d), *args)
 
-    key = ("sp", M, x.C, pk.cout_s, res is not None, bool(sp_out))
-    choice = -1
-    if tile is not None:
-        choice = tile
-    elif AUTOTUNE["on"] and not torch.cuda.is_current_stream_capturing():
-        choice = AUTOTUNE["cache"].get(key)
-        if choice is None:
-            choice = _tune_conv(launch, key, [t for t in SP_TILES if t < 12 or M >= 4096])
-    elif key in AUTOTUNE["cache"]:
-        choice = AUTOTUNE["cache"][key]
+    choice = _choose(("sp", M, x.C, pk.cout_s, res is not None, bool(sp_out)), tile, -1, _sp_tiles, launch, M)
     with _Timed("conv_gemm", 2.0 * M * pk.cin * pk.cout, 4.0 * (M * pk.cin + M * pk.cout * (2 if res is not None else 1) + pk.cout * pk.cin),
                 "M=%d K=%d(1x%d) N=%d pre-split%s%s" % (M, pk.cin, pk.cin, pk.cout, " +res" if res is not None else "", " ->planes" if sp_out else "")) as tm:
         check(launch(choice), "mspi_gemm_sp_fwd")
@@ -813,6 +505,23 @@ def _conv_sp(x, pk, out, res, act, tile, sp_out):
             c = lib.mspi_conv_last_config()
             tm.name = "conv_gemm<%d,%d,dma-presplit,f16x3>" % (c >> 16, (c >> 4) & 0xFFF)
     return out
+
+
+def _conv_kernels(pk, d, M, rg, halo, gate):
+    cands = [1, 2, 3, 4]
+    if pk.prec == PREC_F16X3 and d.sC == 1 and d.C % 4 == 0:
+        cands += [6, 7, 9, 10] + ([8] if pk.cout_s <= 256 else [])
+        if M >= 16384:
+            cands += [12, 13, 14]        # 256-row / 8-wave form of the LDS-DMA kernel
+    if rg is not None:
+        cands.append(THIN)
+    if halo:
+        cands.append(HALO)
+    nk = pk.ldw // 32
+    if SPLITK_ENABLED and gate is None and -(-M // 64) * -(-pk.cout_s // 64) <= 384 and nk >= 32:
+        # few output tiles, long contraction: K slices across workgroups (mspi_conv_splitk_fwd)
+        cands += [SPLITK + S for S in (2, 4, 8) if nk >= 8 * S]
+    return cands
 
 
 def conv(x, pk, out=None, res=None, gate=None, act=None, tile=None, sp_out=False):
@@ -908,31 +617,10 @@ def conv(x, pk, out=None, res=None, gate=None, act=None, tile=None, sp_out=False
         d.tile = t
         return lib.mspi_conv_fwd(C.byref(d), *args)
 
-    choice = -1
     key = (M, taps * pk.cin_s, pk.cout_s, pk.k, pk.stride, pk.prec, d.sC == 1, res is not None, gate is not None, rg is not None, halo)
-    if tile is not None:
-        choice = tile
-    elif AUTOTUNE["on"] and not torch.cuda.is_current_stream_capturing():
-        choice = AUTOTUNE["cache"].get(key)
-        if choice is None:
-            cands = [1, 2, 3, 4]
-            if pk.prec == PREC_F16X3 and d.sC == 1 and Cin % 4 == 0:
-                cands += [6, 7, 9, 10] + ([8] if pk.cout_s <= 256 else [])
-                if M >= 16384:
-                    cands += [12, 13, 14]        # 256-row / 8-wave form of the LDS-DMA kernel
-            if rg is not None:
-                cands.append(THIN)
-            if halo:
-                cands.append(HALO)
-            nk = pk.ldw // 32
-            if SPLITK_ENABLED and gate is None and -(-M // 64) * -(-pk.cout_s // 64) <= 384 and nk >= 32:
-                # few output tiles, long contraction: K slices across workgroups (mspi_conv_splitk_fwd)
-                cands += [SPLITK + S for S in (2, 4, 8) if nk >= 8 * S]
-            choice = _tune_conv(launch, key, cands)
-    elif key in AUTOTUNE["cache"]:
-        choice = AUTOTUNE["cache"][key]
-    elif rg is not None and THIN_DEFAULT:
-        choice = THIN
+    choice = _choose(key, tile, None, _conv_kernels, launch, pk, d, M, rg, halo, gate)
+    if choice is None:      # nothing forced, tuned or cached
+        choice = THIN if rg is not None and THIN_DEFAULT else -1
     if choice == THIN and rg is None:
         raise MspiError("conv: the thin-GEMM kernel does not cover this call")
     if choice == HALO and not halo:
@@ -1181,14 +869,6 @@ def layernorm_for_gemm(x, gamma, beta, eps, *packs):
                                                  for p in packs):
         return layernorm(x, gamma, beta, eps, sp=True)
     return layernorm(x, gamma, beta, eps)
-
-
-def pack_mlp_tail(fc1, fc2, out_scale=None):
-    """LN -> Linear -> GELU -> Linear (+ residual) tail of a ConvNeXt / Swin / MViT block: the fused kernel where it
-    applies (C in {96, 192}, f16x3), else the two GEMM packs.  Use with mlp_tail()."""
-    if mlp_supported(fc1.in_features, fc1.out_features) and fc2.out_features == fc1.in_features:
-        return ("fused", pack_mlp(fc1.weight, fc1.bias, fc2.weight, fc2.bias, out_scale=out_scale))
-    return ("split", pack_conv(fc1.weight, fc1.bias, act=ACT_GELU), pack_conv(fc2.weight, fc2.bias, out_scale=out_scale))
 
 
 def mlp_tail(x, packed, ln, eps, res):
