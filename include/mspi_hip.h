@@ -93,10 +93,26 @@ typedef struct MspiConvDesc {
                                       ldw % 32 == 0 (see below) */
   float w_scale;                   /* F16X3: power-of-two pre-scale of the weights (undone in the epilogue) */
   int32_t tile;                    /* -1: library heuristic; else a kernel instantiation picked by the caller's
-                                      autotuner: 0 128x128/4 waves, 1 128x64, 2 128x32, 3 64x64, 4 128x128/8 waves,
-                                      5 256x128, 6..11 LDS-DMA kernel (128 rows, 4 waves) with 128 / 64 / all (<= 256) /
-                                      96 / 192 / 32 columns per tile, 12..14 its 256-row / 8-wave form with 256 / 192 /
-                                      128 columns (f16x3, 16-B gather only) */
+                                      autotuner, by this table (kTiles in csrc/conv_common.h is its source):
+                                        code   kind                           rows x columns      mspi_gemm_sp_fwd
+                                        0      1 register-staged, 4 waves     128 x 128           -
+                                        1      1                              128 x 64            -
+                                        2      1                              128 x 32            -
+                                        3      1 (split-K: kind 3)            64 x 64             -
+                                        4      2 register-staged, 8 waves     128 x 128           -
+                                        5      2                              256 x 128           -
+                                        6      4 LDS-DMA, 4 waves             128 x 128           128 x 128
+                                        7      4                              128 x 64            128 x 64
+                                        8      4                              128 x all (<= 256)  -
+                                        9      4                              128 x 96            128 x 96
+                                        10     4                              128 x 192           128 x 192
+                                        11     4                              128 x 32            128 x 256
+                                        12     5 LDS-DMA, 8 waves             256 x 256           256 x 256
+                                        13     5                              256 x 192           256 x 192
+                                        14     5                              256 x 128           256 x 128
+                                      Kinds 4 and 5 need f16x3 and the 16-B gather.  "all": one column tile of
+                                      roundup32(Cout) columns.  Last column: the tile mspi_gemm_sp_fwd runs under the
+                                      code (its kinds are 6 and 7), "-" = the heuristic, as for -1. */
   const void* w_blocked;           /* optional (NULL: none), F16X3 only: the same hi/lo weight planes BLOCKED as described at
                                       mspi_gemm_sp_fwd (16 output channels x 32 k = 1 KB contiguous per block, k-fastest,
                                       rows zero-padded to a multiple of 16).  The LDS-DMA kernels (tile 6..14, and the
@@ -120,9 +136,9 @@ int mspi_conv_splitk_fwd(const MspiConvDesc* d, const float* x, const float* w, 
  * input pointer and gate pointer in this process (host only, no GPU call, no pointer dereferenced: x and gate are looked at
  * for NULL and 16-B alignment, a NULL x is refused; the MSPI_CONV_* switches are read once per process):
  *   kind * 10000000 + BM * 10000 + BN * 10 + form
- * kind 1 = register-staged, 4 waves (tiles 0..3), 2 = register-staged, 8 waves (tiles 4, 5), 3 = split-K (64 x 64 tiles),
- * 4 = LDS-DMA, 128 rows (tiles 6..11), 5 = LDS-DMA, 256 rows (tiles 12..14); form = 2 * (scalar gather) + prec for
- * kinds 1..3, 0 = generic gather / 1 = dense (1x1x1, stride 1, no padding) / 2 = dense with the gate for kinds 4 and 5.
+ * kind, BM = rows and BN = columns as in the table at MspiConvDesc.tile, kind 3 = split-K (64 x 64 tiles); form =
+ * 2 * (scalar gather) + prec for kinds 1..3, 0 = generic gather / 1 = dense (1x1x1, stride 1, no padding) / 2 = dense with
+ * the gate for kinds 4 and 5.
  * -1 = a descriptor the launch refuses (mspi_last_error() says why).  The launches select their kernel by this same
  * function; the weight, output and residual pointers are checked at launch only. */
 int mspi_conv_variant(const MspiConvDesc* d, const float* x, const float* gate, int32_t ksplit);
@@ -144,11 +160,6 @@ int mspi_conv_halo_supported(const MspiConvDesc* d);
  * columns per workgroup: the smallest that holds Cout, 192 beyond); -1 = a descriptor or input pointer the launch refuses
  * (mspi_last_error() says why).  Host only; the launch selects by this function. */
 int mspi_conv_halo_variant(const MspiConvDesc* d, const void* x);
-
-/* Which kernel instantiation the calling thread's last mspi_conv_fwd launched:
- * (BM << 16) | (BN << 4) | (8 if 8 waves) | (4 if LDS-DMA staging) | (prec << 1) | (1 if scalar gather, 0 if
- * 16-B vector gather).  For profiling: it names the template instantiation rocprofv3 reports. */
-int mspi_conv_last_config(void);
 
 /* ------------------------------------------------------------------------------------
  * Depthwise convolution, channels-last, bias (= folded BN) + activation fused; optional
@@ -807,7 +818,7 @@ int mspi_clip_resize_norm_fwd(const unsigned char* frames, int32_t N, int32_t Hi
  * conversion work in the loop.  d: as for mspi_conv_fwd with C % 32 == 0, ldw == C, prec f16x3; `w`: the f16 hi/lo weight
  * planes of mspi_conv_fwd BLOCKED the same way (rows = output channels, zero-padded to a multiple of 16; lo plane
  * roundup16(Cout) * K halves after the hi plane; engine.sp_weights builds it);
- * d->tile: -1 heuristic, 6/7/9/10/11 = 128 x {128,64,96,192,256}, 12/13/14 = 256 x {256,192,128}.  The result goes to y
+ * d->tile: the last column of the table at MspiConvDesc.tile.  The result goes to y
  * (fp32 rows, ldy) or, when y_planes != NULL, to blocked output planes (ldys == Cout, Cout % 32 == 0) for the next GEMM.
  * mspi_split_planes_fwd converts fp32 rows. */
 int mspi_layernorm_sp_fwd(const float* x, int64_t ldx, int64_t sample_stride_x, void* planes, int64_t ldo, int64_t plane,

@@ -55,6 +55,39 @@ struct ConvArgs {
 
 constexpr int BK = 32;
 
+// The tile codes of MspiConvDesc.tile (include/mspi_hip.h): the one place a tile is declared.  kind is the leading digit of
+// the variant code (mspi_conv_variant; the pre-split entry point reports kind + 2); bm x bn is the output tile, wm x wn the
+// wave grid (the LDS-DMA kernels give every wave a 32-row slab of all bn columns: wm = waves, wn = 1).  BN_ALL: one column
+// tile holding every output channel (rounded up to 32, <= 256).  sp_bn: the column tile mspi_gemm_sp_fwd runs under this code,
+// 0 = not offered there (code 11 is 128 x 32 on fp32 activations and 128 x 256 on pre-split planes).  slots / eff feed the
+// register tiles' cost model in conv_select: resident workgroups and relative time per unit of work.
+// Adding or removing a tile: its row here and its case in launch_conv_reg (conv_gemm.hip) or launch_conv_dma
+// (conv_gemm_ad.hip), which turn the row's numbers into template arguments.
+enum { TILE_REG4 = 1, TILE_REG8 = 2, TILE_DMA128 = 4, TILE_DMA256 = 5 };
+constexpr int BN_ALL = 1;
+enum { FORM_SP = 3 };   // launch_conv_dma's form for pre-split activation planes, after the forms 0..2 of mspi_conv_variant
+struct Tile { int kind, bm, bn, wm, wn, sp_bn, slots; float eff; };
+static const Tile kTiles[] = {
+    {TILE_REG4, 128, 128, 2, 2, 0, 512, 1.00f},     //  0
+    {TILE_REG4, 128, 64, 2, 2, 0, 512, 1.06f},      //  1
+    {TILE_REG4, 128, 32, 4, 1, 0, 768, 1.30f},      //  2
+    {TILE_REG4, 64, 64, 2, 2, 0, 1024, 1.25f},      //  3  (also the split-K tile)
+    {TILE_REG8, 128, 128, 4, 2, 0, 512, 1.00f},     //  4  32 x 64 per wave
+    {TILE_REG8, 256, 128, 4, 2, 0, 256, 1.10f},     //  5  64 x 64 per wave
+    {TILE_DMA128, 128, 128, 4, 1, 128, 0, 0.f},     //  6
+    {TILE_DMA128, 128, 64, 4, 1, 64, 0, 0.f},       //  7
+    {TILE_DMA128, 128, BN_ALL, 4, 1, 0, 0, 0.f},    //  8  the only way to the 160- and 224-column kernels
+    {TILE_DMA128, 128, 96, 4, 1, 96, 0, 0.f},       //  9
+    {TILE_DMA128, 128, 192, 4, 1, 192, 0, 0.f},     // 10
+    {TILE_DMA128, 128, 32, 4, 1, 256, 0, 0.f},      // 11
+    {TILE_DMA256, 256, 256, 8, 1, 256, 0, 0.f},     // 12
+    {TILE_DMA256, 256, 192, 8, 1, 192, 0, 0.f},     // 13
+    {TILE_DMA256, 256, 128, 8, 1, 128, 0, 0.f},     // 14
+};
+constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+inline bool tile_is_dma(const Tile& t) { return t.kind >= TILE_DMA128; }
+inline int variant_code(int kind, int bm, int bn, int form) { return kind * 10000000 + bm * 10000 + bn * 10 + form; }
+
 // XCD-aware, bijective block remap: blocks dealt to one XCD (bid % 8) get consecutive logical ids, so the
 // N-tiles that re-read one A row panel (and the M-tiles that re-read one weight panel) share that XCD's L2.
 __device__ __forceinline__ int xcd_logical_block(int bid, int nwg) {

@@ -419,13 +419,9 @@ using namespace mspi;
 
 namespace mspi {
 int dma_bn(long Ml, int Cout, int force_bn);
-bool sp_tile_ok(int rows, int bn);
-int launch_conv_dma(ConvArgs& a, long Ml, int rows, int bn, int form, int* cfg, hipStream_t s);
-int launch_conv_sp(ConvArgs& a, long Ml, int bn, int rows, int* cfg, hipStream_t s);
+bool dma_tile_ok(int rows, int bn, bool presplit);
+int launch_conv_dma(ConvArgs& a, long Ml, int rows, int bn, int form, hipStream_t s);
 }
-
-static thread_local int g_last_cfg = 0;
-extern "C" int mspi_conv_last_config(void) { return g_last_cfg; }
 
 namespace mspi {
 // y = act( sum_z ws[z] + bias + res ): the K slices' partial sums, added in slice order (bitwise reproducible)
@@ -458,18 +454,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 }  // namespace mspi
 
-// Register-staged tiles 0..5: {BM, BN, resident workgroups, relative rate}; 4 and 5 run 8 waves.
-struct Cfg { int bm, bn, slots; float eff; };
-static const Cfg kCfgs[6] = {{128, 128, 512, 1.00f}, {128, 64, 512, 1.06f}, {128, 32, 768, 1.30f}, {64, 64, 1024, 1.25f},
-                             {128, 128, 512, 1.00f}, {256, 128, 256, 1.10f}};
-
-// The kernel instantiation of a conv launch (include/mspi_hip.h, mspi_conv_variant): kind * 10^7 + BM * 10^4 + BN * 10 + form.
-// kind 1 = register-staged, 4 waves (tiles 0..3), 2 = register-staged, 8 waves (tiles 4, 5), 3 = split-K (64 x 64), 4 = LDS-DMA,
-// 128 rows (tiles 6..11), 5 = LDS-DMA, 256 rows (tiles 12..14); form = 2 * scalar gather + prec for kinds 1..3, 0 generic /
-// 1 dense / 2 gate for kinds 4 and 5.  Every check that does not need the weight / output / residual pointers lives here; a
-// descriptor the launch refuses gives -1 with mspi_last_error() set.  conv_fwd_impl switches on this code, so the query cannot
-// drift from what runs.  `tile` receives the register tile (0..5) of kinds 1..3.
-static int conv_select(const MspiConvDesc* d, const float* x, const float* gate, int ksplit, int& tile) {
+// The kernel instantiation of a conv launch (include/mspi_hip.h, mspi_conv_variant): kind * 10^7 + BM * 10^4 + BN * 10 + form,
+// kind and tile shape from kTiles (conv_common.h), kind 3 = split-K (the 64 x 64 register tile); form = 2 * scalar gather + prec
+// for kinds 1..3, 0 generic / 1 dense / 2 gate for kinds 4 and 5.  Every check that does not need the weight / output /
+// residual pointers lives here; a descriptor the launch refuses gives -1 with mspi_last_error() set.  conv_fwd_impl launches
+// what this code names, so the query cannot drift from what runs.
+static int conv_select(const MspiConvDesc* d, const float* x, const float* gate, int ksplit) {
   MSPI_REQUIRE(x, "mspi_conv_fwd: null argument");      // aligned16(NULL) holds: a NULL input would pass for a 16-B gather
   MSPI_REQUIRE(d->N > 0 && d->T > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->Cout > 0, "mspi_conv_fwd: empty extent");
   MSPI_REQUIRE(d->kT > 0 && d->kH > 0 && d->kW > 0 && d->strT > 0 && d->strH > 0 && d->strW > 0 && d->padT >= 0 &&
@@ -504,8 +494,7 @@ static int conv_select(const MspiConvDesc* d, const float* x, const float* gate,
                  "mspi_conv_splitk_fwd: no gate; Cout / ldy / ldr multiples of 4; 16-B aligned pointers");
     MSPI_REQUIRE(ksplit <= 64 && ksplit <= (d->ldw + BK - 1) / BK, "mspi_conv_splitk_fwd: ksplit = %d", ksplit);
     MSPI_REQUIRE(((Ml + 63) / 64) * ((d->Cout + 63) / 64) < (1L << 31), "mspi_conv_splitk_fwd: grid too large");
-    tile = 3;
-    return 30000000 + 64 * 10000 + 64 * 10 + form;
+    return variant_code(3, 64, 64, form);
   }
 
   // LDS-DMA form (conv_gemm_ad.hip): measured faster than the register-staged kernel on deep implicit GEMMs
@@ -514,19 +503,20 @@ static int conv_select(const MspiConvDesc* d, const float* x, const float* gate,
   static const int dma_mode = getenv("MSPI_CONV_DMA") ? atoi(getenv("MSPI_CONV_DMA")) : 1;   // 0 never, 1 auto, 2 always
   const bool deep_conv = (long)d->kT * d->kH * d->kW > 1 && K >= 2048 && Ml >= 16384;
   const bool dma_ok = d->prec == PREC_F16X3 && v4;
-  MSPI_REQUIRE(d->tile >= -1 && d->tile <= 14 && (d->tile < 6 || dma_ok) && (d->tile != 8 || d->Cout <= 256),
+  const Tile* forced = d->tile >= 0 && d->tile < kNumTiles ? &kTiles[d->tile] : nullptr;
+  MSPI_REQUIRE(d->tile >= -1 && d->tile < kNumTiles && (!forced || !tile_is_dma(*forced) || dma_ok) &&
+                   (!forced || forced->bn != BN_ALL || d->Cout <= 256),
                "mspi_conv_fwd: tile %d not available for this call", d->tile);
   const int dform = gate ? 2 : dense ? 1 : 0;
-  if (d->tile >= 12) {   // LDS-DMA kernel with a 256-row tile and 8 waves sharing one weight tile
-    static const int bn8[3] = {256, 192, 128};
-    const int bn = bn8[d->tile - 12];
-    MSPI_REQUIRE(((Ml + 255) / 256) * ((d->Cout + bn - 1) / bn) < (1L << 31), "mspi_conv_fwd: tile %d could not be launched", d->tile);
-    return 50000000 + 256 * 10000 + bn * 10 + dform;
+  if (forced && forced->kind == TILE_DMA256) {   // LDS-DMA kernel with a 256-row tile and 8 waves sharing one weight tile
+    const int bm = forced->bm, bn = forced->bn;
+    MSPI_REQUIRE(((Ml + bm - 1) / bm) * ((d->Cout + bn - 1) / bn) < (1L << 31), "mspi_conv_fwd: tile %d could not be launched", d->tile);
+    return variant_code(TILE_DMA256, bm, bn, dform);
   }
-  if (dma_ok && (d->tile >= 6 || (d->tile < 0 && (dma_mode == 2 || (dma_mode == 1 && deep_conv))))) {
-    static const int dma_bn_of[6] = {128, 64, 1, 96, 192, 32};   // tile 6..11 (1 = all columns in one tile)
-    const int bn = dma_bn(Ml, d->Cout, d->tile >= 6 ? dma_bn_of[d->tile - 6] : 0);
-    if (bn > 0 && ((Ml + 127) / 128) * ((d->Cout + bn - 1) / bn) < (1L << 31)) return 40000000 + 128 * 10000 + bn * 10 + dform;
+  const bool forced_dma = forced && tile_is_dma(*forced);
+  if (dma_ok && (forced_dma || (d->tile < 0 && (dma_mode == 2 || (dma_mode == 1 && deep_conv))))) {
+    const int bn = dma_bn(Ml, d->Cout, forced_dma ? forced->bn : 0);
+    if (bn > 0 && ((Ml + 127) / 128) * ((d->Cout + bn - 1) / bn) < (1L << 31)) return variant_code(TILE_DMA128, 128, bn, dform);
     // heuristic: no LDS-DMA tile for this request, the register-staged kernel takes it
     MSPI_REQUIRE(d->tile < 0, "mspi_conv_fwd: tile %d could not be launched", d->tile);
   }
@@ -538,96 +528,102 @@ static int conv_select(const MspiConvDesc* d, const float* x, const float* gate,
   static const int force = getenv("MSPI_CONV_TILE") ? atoi(getenv("MSPI_CONV_TILE")) : -1;
   int best = 3;
   double best_cost = 1e300;
-  for (int i = 0; i < 4; ++i) {
-    const long tm = (Ml + kCfgs[i].bm - 1) / kCfgs[i].bm, tn = (d->Cout + kCfgs[i].bn - 1) / kCfgs[i].bn;
-    const long blocks = tm * tn;
-    double rounds = (double)blocks / kCfgs[i].slots;
-    if (rounds < 6.0) rounds = (double)((blocks + kCfgs[i].slots - 1) / kCfgs[i].slots);
-    const double cost = rounds * kCfgs[i].bm * kCfgs[i].bn * kCfgs[i].eff * ((double)K + 192.0);
+  for (int i = 0; i < kNumTiles; ++i) {
+    const Tile& t = kTiles[i];
+    if (t.kind != TILE_REG4) continue;
+    const long blocks = ((Ml + t.bm - 1) / t.bm) * ((d->Cout + t.bn - 1) / t.bn);
+    double rounds = (double)blocks / t.slots;
+    if (rounds < 6.0) rounds = (double)((blocks + t.slots - 1) / t.slots);
+    const double cost = rounds * t.bm * t.bn * t.eff * ((double)K + 192.0);
     if (cost < best_cost) { best_cost = cost; best = i; }
   }
   if (best == 0 && !getenv("MSPI_CONV_4WAVE")) best = 4;   // 128x128 runs best with 8 waves (32x64 per wave, 4 waves/SIMD)
-  if (force >= 0 && force < 6) best = force;
-  if (d->tile >= 0) best = d->tile;
-  const long nb = ((Ml + kCfgs[best].bm - 1) / kCfgs[best].bm) * ((d->Cout + kCfgs[best].bn - 1) / kCfgs[best].bn);
-  MSPI_REQUIRE(nb < (1L << 31), "mspi_conv_fwd: grid too large");
-  tile = best;
-  return (best >= 4 ? 20000000 : 10000000) + kCfgs[best].bm * 10000 + kCfgs[best].bn * 10 + form;
+  if (force >= 0 && force < kNumTiles && !tile_is_dma(kTiles[force])) best = force;
+  if (forced) best = d->tile;
+  const Tile& t = kTiles[best];
+  MSPI_REQUIRE(((Ml + t.bm - 1) / t.bm) * ((d->Cout + t.bn - 1) / t.bn) < (1L << 31), "mspi_conv_fwd: grid too large");
+  return variant_code(t.kind, t.bm, t.bn, form);
 }
 
 extern "C" int mspi_conv_variant(const MspiConvDesc* d, const float* x, const float* gate, int32_t ksplit) {
   MSPI_REQUIRE(d, "mspi_conv_variant: null descriptor");
-  int tile = 0;
-  return conv_select(d, x, gate, ksplit, tile);
+  return conv_select(d, x, gate, ksplit);
 }
 
-static int conv_fwd_impl(const MspiConvDesc* d, const float* x, const float* w, const float* bias, const float* res,
-                         const float* gate, float* y, float* ws, int ksplit, mspi_stream_t stream) {
-  MSPI_REQUIRE(d && x && w && y, "mspi_conv_fwd: null argument");
-  MSPI_REQUIRE(!ws || ksplit >= 2, "mspi_conv_splitk_fwd: ksplit = %d", ksplit);
-  int tile = 0;
-  const int variant = conv_select(d, x, gate, ws ? ksplit : 1, tile);
-  if (variant < 0) return variant;
-  const int kind = variant / 10000000, form = variant % 10;
-  const bool v4 = kind <= 3 ? (form & 2) == 0 : true;
-  MSPI_REQUIRE(aligned16(w), "mspi_conv_fwd: weight rows must be 16-B aligned, ldw >= K");
-  MSPI_REQUIRE(!res || d->ldr >= d->Cout, "mspi_conv_fwd: ldr < Cout");
-  const int To = d->To, Ho = d->Ho, Wo = d->Wo;
-  const long K = (long)d->kT * d->kH * d->kW * d->C;
-  const long Ml = (long)d->N * To * Ho * Wo;
-
-  ConvArgs a;
+// The kernels' argument block as the descriptor gives it: a conv on fp32 activations, no split-K, general gather.  Callers
+// set what differs (planes, wb, ws / ksplit, dense_rows, dbg); tiles_n / nblocks belong to the launch.
+static ConvArgs conv_args(const MspiConvDesc* d, const float* x, const float* w, const float* bias, const float* res,
+                          const float* gate, float* y) {
+  ConvArgs a = {};
   a.x = x; a.w = w; a.bias = bias; a.res = res; a.gate = gate; a.y = y;
   a.N = d->N; a.T = d->T; a.H = d->H; a.W = d->W; a.C = d->C;
   a.sN = d->sN; a.sT = d->sT; a.sH = d->sH; a.sW = d->sW; a.sC = d->sC;
   a.kT = d->kT; a.kH = d->kH; a.kW = d->kW;
   a.strT = d->strT; a.strH = d->strH; a.strW = d->strW;
   a.padT = d->padT; a.padH = d->padH; a.padW = d->padW;
-  a.To = To; a.Ho = Ho; a.Wo = Wo; a.Cout = d->Cout;
+  a.To = (d->T + 2 * d->padT - d->kT) / d->strT + 1;      // (mspi_conv_fwd checks d->To, Ho, Wo against these; mspi_gemm_sp_fwd
+  a.Ho = (d->H + 2 * d->padH - d->kH) / d->strH + 1;      //  is 1x1x1 and does not read them)
+  a.Wo = (d->W + 2 * d->padW - d->kW) / d->strW + 1;
+  a.Cout = d->Cout;
   a.ldy = d->ldy; a.ldw = d->ldw; a.ldr = d->ldr; a.act = d->act;
-  a.M = (int)Ml; a.K = (int)K; a.rows_per_sample = To * Ho * Wo;
+  a.rows_per_sample = a.To * a.Ho * a.Wo;
+  a.M = d->N * a.rows_per_sample; a.K = d->kT * d->kH * d->kW * d->C;      // both < 2^31: checked by the selection
   a.out_scale = d->prec == PREC_F16X3 ? 1.0f / d->w_scale : 1.0f;
   a.status = g_status_word;
+  a.ksplit = 1;
+  return a;
+}
+
+// Register-staged launch of the kTiles row with this kind and shape (split-K: ws set, the 64 x 64 row).  Returns 0 when
+// launched, -100 when the table has no such row or the row no case below.
+static int launch_conv_reg(ConvArgs& a, int kind, int bm, int bn, bool v4, int prec, hipStream_t s) {
+  const Tile* t = nullptr;
+  for (const Tile& r : kTiles)
+    if (r.kind == kind && r.bm == bm && r.bn == bn) t = &r;
+  if (!t) return -100;
+  a.tiles_n = (a.Cout + bn - 1) / bn;
+  a.nblocks = (int)((((long)a.M + bm - 1) / bm) * a.tiles_n);
+#define REG_CASE(BM, BN, WM, WN) case (BM << 20) | (BN << 8) | (WM << 4) | WN: launch_cfg<BM, BN, WM, WN>(a, v4, prec, s); return 0;
+  switch ((bm << 20) | (bn << 8) | (t->wm << 4) | t->wn) {
+    REG_CASE(128, 128, 2, 2) REG_CASE(128, 64, 2, 2) REG_CASE(128, 32, 4, 1) REG_CASE(64, 64, 2, 2)
+    REG_CASE(128, 128, 4, 2) REG_CASE(256, 128, 4, 2)
+    default: return -100;
+  }
+#undef REG_CASE
+}
+
+static int conv_fwd_impl(const MspiConvDesc* d, const float* x, const float* w, const float* bias, const float* res,
+                         const float* gate, float* y, float* ws, int ksplit, mspi_stream_t stream) {
+  MSPI_REQUIRE(d && x && w && y, "mspi_conv_fwd: null argument");
+  MSPI_REQUIRE(!ws || ksplit >= 2, "mspi_conv_splitk_fwd: ksplit = %d", ksplit);
+  const int variant = conv_select(d, x, gate, ws ? ksplit : 1);
+  if (variant < 0) return variant;
+  const int kind = variant / 10000000, bm = (variant / 10000) % 1000, bn = (variant / 10) % 1000, form = variant % 10;
+  const bool v4 = kind <= 3 ? (form & 2) == 0 : true;
+  MSPI_REQUIRE(aligned16(w), "mspi_conv_fwd: weight rows must be 16-B aligned, ldw >= K");
+  MSPI_REQUIRE(!res || d->ldr >= d->Cout, "mspi_conv_fwd: ldr < Cout");
+
+  ConvArgs a = conv_args(d, x, w, bias, res, gate, y);
   static const int dbg = getenv("MSPI_CONV_DBG") ? atoi(getenv("MSPI_CONV_DBG")) : 0;
   a.dbg = dbg;
   a.ws = ws; a.ksplit = ksplit;
   a.dense_rows = (d->kT == 1 && d->kH == 1 && d->kW == 1 && d->strT == 1 && d->strH == 1 && d->strW == 1 && d->padT == 0 && d->padH == 0 &&
                   d->padW == 0 && d->sC == 1 && d->sH == (int64_t)d->W * d->sW && d->sT == (int64_t)d->H * d->sH &&
                   d->sN == (int64_t)d->T * d->sT) ? 1 : 0;
-  a.wb = (d->prec == PREC_F16X3) ? (const _Float16*)d->w_blocked : nullptr; a.xs = nullptr; a.ldxs = 0; a.xplane = 0; a.ys = nullptr; a.ldys = 0; a.yplane = 0;
+  a.wb = (d->prec == PREC_F16X3) ? (const _Float16*)d->w_blocked : nullptr;
   hipStream_t s = (hipStream_t)stream;
   if (kind == 3) {
     MSPI_REQUIRE((!res || (d->ldr & 3) == 0) && aligned16(y) && aligned16(ws) && (!res || aligned16(res)) && (!bias || aligned16(bias)),
                  "mspi_conv_splitk_fwd: no gate; Cout / ldy / ldr multiples of 4; 16-B aligned pointers");
-    a.tiles_n = (d->Cout + 63) / 64;
-    a.nblocks = (int)(((Ml + 63) / 64) * a.tiles_n);
-    g_last_cfg = (64 << 16) | (64 << 4) | (d->prec << 1) | (v4 ? 0 : 1);
-    launch_cfg<64, 64, 2, 2>(a, v4, d->prec, s);
-    const long total = Ml * (d->Cout >> 2);
+    MSPI_REQUIRE(launch_conv_reg(a, TILE_REG4, bm, bn, v4, d->prec, s) == 0, "mspi_conv_splitk_fwd: variant %d could not be launched", variant);
+    const long total = (long)a.M * (d->Cout >> 2);
     const long blocks = (total + 255) / 256;
     hipLaunchKernelGGL(mspi::splitk_reduce_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, ws, ksplit,
-                       Ml, d->Cout, bias, res, (long)d->ldr, y, (long)d->ldy, d->act, mspi::g_status_word);
+                       (long)a.M, d->Cout, bias, res, (long)d->ldr, y, (long)d->ldy, d->act, mspi::g_status_word);
     return check_launch("mspi_conv_splitk_fwd");
   }
-  if (kind >= 4) {
-    int cfg = 0;
-    const int rc = launch_conv_dma(a, Ml, kind == 5 ? 256 : 128, (variant / 10) % 1000, form, &cfg, s);
-    MSPI_REQUIRE(rc == 0, "mspi_conv_fwd: variant %d could not be launched", variant);
-    g_last_cfg = cfg;
-    return check_launch("mspi_conv_fwd");
-  }
-  const int BMs = kCfgs[tile].bm, BNs = kCfgs[tile].bn;
-  a.tiles_n = (d->Cout + BNs - 1) / BNs;
-  a.nblocks = (int)(((Ml + BMs - 1) / BMs) * a.tiles_n);
-  g_last_cfg = (BMs << 16) | (BNs << 4) | (tile >= 4 ? 8 : 0) | (d->prec << 1) | (v4 ? 0 : 1);
-  switch (tile) {
-    case 0: launch_cfg<128, 128, 2, 2>(a, v4, d->prec, s); break;
-    case 1: launch_cfg<128, 64, 2, 2>(a, v4, d->prec, s); break;
-    case 2: launch_cfg<128, 32, 4, 1>(a, v4, d->prec, s); break;
-    case 4: launch_cfg<128, 128, 4, 2>(a, v4, d->prec, s); break;   // 8 waves, 32x64 per wave
-    case 5: launch_cfg<256, 128, 4, 2>(a, v4, d->prec, s); break;   // 8 waves, 64x64 per wave
-    default: launch_cfg<64, 64, 2, 2>(a, v4, d->prec, s); break;
-  }
+  const int rc = kind >= TILE_DMA128 ? launch_conv_dma(a, a.M, bm, bn, form, s) : launch_conv_reg(a, kind, bm, bn, v4, d->prec, s);
+  MSPI_REQUIRE(rc == 0, "mspi_conv_fwd: variant %d could not be launched", variant);
   return check_launch("mspi_conv_fwd");
 }
 
@@ -709,8 +705,9 @@ extern "C" int mspi_join_planes_fwd(const void* planes, int64_t ldi, int64_t pla
 }
 
 // The instantiation mspi_gemm_sp_fwd runs (include/mspi_hip.h, mspi_gemm_sp_variant): kind * 10^7 + BM * 10^4 + BN * 10 + form,
-// kind 6 = 128 rows / 4 waves, 7 = 256 rows / 8 waves (conv_gemm_dma_kernel<BN, false, true, NW, true>), form 0 = fp32 rows
-// out, 1 = blocked planes out; -1 = a descriptor the launch refuses.  mspi_gemm_sp_fwd switches on this code.
+// kind = the kTiles row's kind + 2 (6 = 128 rows / 4 waves, 7 = 256 rows / 8 waves: conv_gemm_dma_kernel<BN, false, true, NW,
+// true>), BN its sp_bn, form 0 = fp32 rows out, 1 = blocked planes out; -1 = a descriptor the launch refuses.
+// mspi_gemm_sp_fwd launches what this code names.
 static int gemm_sp_select(const MspiConvDesc* d, bool planes_out) {
   MSPI_REQUIRE(d->kT == 1 && d->kH == 1 && d->kW == 1 && d->strT == 1 && d->strH == 1 && d->strW == 1 && d->padT == 0 &&
                    d->padH == 0 && d->padW == 0, "mspi_gemm_sp_fwd: a plain GEMM on rows (1x1x1, stride 1, no padding)");
@@ -720,21 +717,12 @@ static int gemm_sp_select(const MspiConvDesc* d, bool planes_out) {
   MSPI_REQUIRE(d->N > 0 && d->T > 0 && d->H > 0 && d->W > 0 && d->Cout > 0 && Ml < (1L << 31), "mspi_gemm_sp_fwd: bad extent");
   MSPI_REQUIRE(!planes_out || (d->Cout % 32) == 0, "mspi_gemm_sp_fwd: blocked output planes need Cout %% 32 == 0");
   MSPI_REQUIRE(planes_out || d->ldy >= d->Cout, "mspi_gemm_sp_fwd: ldy < Cout");
-  int bn, rows = 128;
-  switch (d->tile) {
-    case 6: bn = 128; break;
-    case 7: bn = 64; break;
-    case 9: bn = 96; break;
-    case 10: bn = 192; break;
-    case 11: bn = 256; break;
-    case 12: bn = 256; rows = 256; break;
-    case 13: bn = 192; rows = 256; break;
-    case 14: bn = 128; rows = 256; break;
-    default: bn = d->Cout <= 64 ? 64 : (d->Cout % 192 == 0 ? 192 : 128); break;
-  }
-  MSPI_REQUIRE(sp_tile_ok(rows, bn) && ((Ml + rows - 1) / rows) * ((d->Cout + bn - 1) / bn) < (1L << 31),
+  const Tile* t = d->tile >= 0 && d->tile < kNumTiles && kTiles[d->tile].sp_bn ? &kTiles[d->tile] : nullptr;
+  const int rows = t ? t->bm : 128;
+  const int bn = t ? t->sp_bn : d->Cout <= 64 ? 64 : (d->Cout % 192 == 0 ? 192 : 128);      // any other code: the heuristic
+  MSPI_REQUIRE(dma_tile_ok(rows, bn, true) && ((Ml + rows - 1) / rows) * ((d->Cout + bn - 1) / bn) < (1L << 31),
                "mspi_gemm_sp_fwd: tile %d could not be launched", d->tile);
-  return (rows == 256 ? 70000000 : 60000000) + rows * 10000 + bn * 10 + (planes_out ? 1 : 0);
+  return variant_code((t ? t->kind : TILE_DMA128) + 2, rows, bn, planes_out ? 1 : 0);
 }
 
 extern "C" int mspi_gemm_sp_variant(const MspiConvDesc* d, const void* y_planes) {
@@ -757,25 +745,11 @@ extern "C" int mspi_gemm_sp_fwd(const MspiConvDesc* d, const void* x_planes, int
                               aligned16(y_planes)), "mspi_gemm_sp_fwd: blocked output planes need Cout %% 32 == 0, ldys == Cout, plane >= roundup16(M) * Cout");
   MSPI_REQUIRE(!y || d->ldy >= d->Cout, "mspi_gemm_sp_fwd: ldy < Cout");
   MSPI_REQUIRE(!res || d->ldr >= d->Cout, "mspi_gemm_sp_fwd: ldr < Cout");
-  ConvArgs a;
-  a.x = nullptr; a.w = w; a.bias = bias; a.res = res; a.gate = nullptr; a.y = y;
-  a.N = d->N; a.T = d->T; a.H = d->H; a.W = d->W; a.C = d->C;
-  a.sN = a.sT = a.sH = a.sW = 0; a.sC = 1;
-  a.kT = a.kH = a.kW = 1; a.strT = a.strH = a.strW = 1; a.padT = a.padH = a.padW = 0;
-  a.To = d->T; a.Ho = d->H; a.Wo = d->W; a.Cout = d->Cout;
-  a.ldy = d->ldy; a.ldw = d->ldw; a.ldr = d->ldr; a.act = d->act;
-  a.M = (int)Ml; a.K = d->C; a.rows_per_sample = d->T * d->H * d->W;
-  a.out_scale = 1.0f / d->w_scale;
-  a.status = g_status_word;
-  a.dbg = 0; a.ws = nullptr; a.ksplit = 1;
+  ConvArgs a = conv_args(d, nullptr, w, bias, res, nullptr, y);      // (blocked weights come through `w`; wb stays NULL)
   a.dense_rows = 1;
-  a.wb = nullptr;      // (the pre-split form takes blocked weights through `w`)
   a.xs = (const _Float16*)x_planes; a.ldxs = ldx; a.xplane = xplane;
   a.ys = (_Float16*)y_planes; a.ldys = ldys; a.yplane = yplane;
-  const int rows = (variant / 10000) % 1000, bn = (variant / 10) % 1000;
-  int cfg = 0;
-  const int rc = launch_conv_sp(a, Ml, bn, rows, &cfg, (hipStream_t)stream);
+  const int rc = launch_conv_dma(a, Ml, (variant / 10000) % 1000, (variant / 10) % 1000, FORM_SP, (hipStream_t)stream);
   MSPI_REQUIRE(rc == 0, "mspi_gemm_sp_fwd: tile %d could not be launched", d->tile);
-  g_last_cfg = cfg;
   return check_launch("mspi_gemm_sp_fwd");
 }

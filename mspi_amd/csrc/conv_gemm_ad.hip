@@ -388,7 +388,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_gemm_dma_kernel(const ConvArg
 }
 
 // form (mspi_conv_variant): 0 = generic gather, 1 = DENSE (1x1x1, stride 1, no padding), 2 = DENSE with the squeeze-excite gate
-template <int BN, int NW = 4>
+template <int BN, int NW>
 static void launch_bn(const ConvArgs& a, int form, hipStream_t s) {
   const dim3 g(a.nblocks), b(64 * NW);
   if (form == 2) hipLaunchKernelGGL((conv_gemm_dma_kernel<BN, true, true, NW>), g, b, 0, s, a);
@@ -396,87 +396,53 @@ static void launch_bn(const ConvArgs& a, int form, hipStream_t s) {
   else hipLaunchKernelGGL((conv_gemm_dma_kernel<BN, false, false, NW>), g, b, 0, s, a);
 }
 
-// pre-split activations (mspi_gemm_sp_fwd): dense GEMM on rows, A = two f16 planes
+// pre-split activations (mspi_gemm_sp_fwd, form FORM_SP): dense GEMM on rows, A = two f16 planes
 template <int BN, int NW>
 static void launch_sp(const ConvArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((conv_gemm_dma_kernel<BN, false, true, NW, true>), dim3(a.nblocks), dim3(64 * NW), 0, s, a);
 }
 
-// the instantiations mspi_gemm_sp_fwd has: 128 rows x {64, 96, 128, 192, 256}, 256 rows x {128, 192, 256}
-bool sp_tile_ok(int rows, int bn) {
-  return rows == 256 ? (bn == 128 || bn == 192 || bn == 256) : rows == 128 && (bn == 64 || bn == 96 || bn == 128 || bn == 192 || bn == 256);
-}
-
-// returns 0 when launched, -100 when no instantiation matches (the selection in conv_gemm.hip rules that out)
-int launch_conv_sp(ConvArgs& a, long Ml, int bn, int rows, int* cfg, hipStream_t s) {
-  if (!sp_tile_ok(rows, bn)) return -100;
-  a.tiles_n = (int)((a.Cout + bn - 1) / bn);
-  const long nb = ((Ml + rows - 1) / rows) * a.tiles_n;
-  if (nb >= (1L << 31)) return -100;
-  a.nblocks = (int)nb;
-  *cfg = (rows << 16) | (bn << 4) | (rows == 256 ? 8 : 0) | (PREC_F16X3 << 1) | 4;
-  if (rows == 256) {
-    switch (bn) {
-      case 128: launch_sp<128, 8>(a, s); break;
-      case 192: launch_sp<192, 8>(a, s); break;
-      default: launch_sp<256, 8>(a, s); break;
-    }
-    return 0;
+// whether a row of kTiles gives the LDS-DMA kernel this shape, on fp32 activations or (presplit) at mspi_gemm_sp_fwd
+bool dma_tile_ok(int rows, int bn, bool presplit) {
+  for (const Tile& t : kTiles) {
+    if (!tile_is_dma(t) || t.bm != rows) continue;
+    if (presplit ? t.sp_bn == bn : t.bn == bn || (t.bn == BN_ALL && bn >= 32 && bn <= 256 && bn % 32 == 0)) return true;
   }
-  switch (bn) {
-    case 64: launch_sp<64, 4>(a, s); break;
-    case 96: launch_sp<96, 4>(a, s); break;
-    case 128: launch_sp<128, 4>(a, s); break;
-    case 192: launch_sp<192, 4>(a, s); break;
-    default: launch_sp<256, 4>(a, s); break;
-  }
-  return 0;
+  return false;
 }
 
 // Column tile of the 128-row LDS-DMA kernel.  force_bn: 0 = heuristic (or MSPI_CONV_BN), else the column tile (a multiple of
-// 32 up to 256; 1 = "all columns in one tile").  Returns 0 when no instantiation covers the request.
+// 32 up to 256; BN_ALL = "all columns in one tile").  Returns 0 when no instantiation covers the request.
 int dma_bn(long Ml, int Cout, int force_bn_arg) {
   const long tm = (Ml + 127) / 128;
   const long t128 = (Cout + 127) / 128, t64 = (Cout + 63) / 64;
   static const int env_bn = getenv("MSPI_CONV_BN") ? atoi(getenv("MSPI_CONV_BN")) : 0;
   int bn = force_bn_arg ? force_bn_arg : env_bn;
-  if (bn == 1) bn = (Cout + 31) / 32 * 32;   // one column tile holding every output channel: the activations are fetched exactly once
+  if (bn == BN_ALL) bn = (Cout + 31) / 32 * 32;   // one column tile holding every output channel: the activations are fetched exactly once
   if (bn == 0) bn = (t64 * 64 < t128 * 128 || tm * t128 < 384) ? 64 : 128;   // less padding, or a grid that fills the chip
-  switch (bn) {
-    case 32: case 64: case 96: case 128: case 160: case 192: case 224: case 256: return bn;
-    default: return 0;
-  }
+  return dma_tile_ok(128, bn, false) ? bn : 0;
 }
 
-// LDS-DMA launch of the instantiation the selection picked: rows 128 (4 waves, BN 32..256) or 256 (8 waves, BN 128 / 192 /
-// 256), form as at launch_bn.  Returns 0 when launched, -100 when no instantiation matches.
-int launch_conv_dma(ConvArgs& a, long Ml, int rows, int bn, int form, int* cfg, hipStream_t s) {
+// LDS-DMA launch of the instantiation the selection picked: rows 128 (4 waves) or 256 (8 waves), form as at launch_bn or
+// FORM_SP.  Returns 0 when launched, -100 when no instantiation matches (the selection in conv_gemm.hip rules that out).
+int launch_conv_dma(ConvArgs& a, long Ml, int rows, int bn, int form, hipStream_t s) {
+  const bool sp = form == FORM_SP;
+  if (!dma_tile_ok(rows, bn, sp)) return -100;
   a.tiles_n = (int)((a.Cout + bn - 1) / bn);
   const long nb = ((Ml + rows - 1) / rows) * a.tiles_n;
   if (nb >= (1L << 31)) return -100;
   a.nblocks = (int)nb;
-  *cfg = (rows << 16) | (bn << 4) | (rows == 256 ? 8 : 0) | (PREC_F16X3 << 1) | 4;   // loader code 4 = LDS-DMA
-  if (rows == 256) {
-    switch (bn) {
-      case 128: launch_bn<128, 8>(a, form, s); break;
-      case 192: launch_bn<192, 8>(a, form, s); break;
-      case 256: launch_bn<256, 8>(a, form, s); break;
-      default: return -100;
-    }
-    return 0;
-  }
-  switch (bn) {
-    case 32: launch_bn<32>(a, form, s); break;
-    case 64: launch_bn<64>(a, form, s); break;
-    case 96: launch_bn<96>(a, form, s); break;
-    case 128: launch_bn<128>(a, form, s); break;
-    case 160: launch_bn<160>(a, form, s); break;
-    case 192: launch_bn<192>(a, form, s); break;
-    case 224: launch_bn<224>(a, form, s); break;
-    case 256: launch_bn<256>(a, form, s); break;
+#define SP_CASE(NW, BN) case 100000 + NW * 1000 + BN: launch_sp<BN, NW>(a, s); return 0;
+#define DMA_CASE(NW, BN) case NW * 1000 + BN: launch_bn<BN, NW>(a, form, s); return 0;
+  switch ((sp ? 100000 : 0) + rows / 32 * 1000 + bn) {
+    SP_CASE(8, 128) SP_CASE(8, 192) SP_CASE(8, 256)
+    SP_CASE(4, 64) SP_CASE(4, 96) SP_CASE(4, 128) SP_CASE(4, 192) SP_CASE(4, 256)
+    DMA_CASE(8, 128) DMA_CASE(8, 192) DMA_CASE(8, 256)
+    DMA_CASE(4, 32) DMA_CASE(4, 64) DMA_CASE(4, 96) DMA_CASE(4, 128) DMA_CASE(4, 160) DMA_CASE(4, 192) DMA_CASE(4, 224) DMA_CASE(4, 256)
     default: return -100;
   }
-  return 0;
+#undef SP_CASE
+#undef DMA_CASE
 }
 
 }  // namespace mspi

@@ -447,15 +447,35 @@ def _out_extent(T, H, W, k, s, p):
     return ((T + 2 * p[0] - k[0]) // s[0] + 1, (H + 2 * p[1] - k[1]) // s[1] + 1, (W + 2 * p[2] - k[2]) // s[2] + 1)
 
 
-# mspi_gemm_sp_fwd: 128 x {128,64,96,192,256}, 256 x {256,192,128}
-SP_TILES = (6, 7, 9, 10, 11, 12, 13, 14)
+# The tile codes of MspiConvDesc.tile, as kTiles in csrc/conv_common.h declares them: code -> (kind, BM, BN), kind the leading
+# digit of the variant code.  BN 0 = every output channel in one column tile.
+REG4, REG8, DMA128, DMA256 = 1, 2, 4, 5
+TILES = {0: (REG4, 128, 128), 1: (REG4, 128, 64), 2: (REG4, 128, 32), 3: (REG4, 64, 64), 4: (REG8, 128, 128), 5: (REG8, 256, 128),
+         6: (DMA128, 128, 128), 7: (DMA128, 128, 64), 8: (DMA128, 128, 0), 9: (DMA128, 128, 96), 10: (DMA128, 128, 192),
+         11: (DMA128, 128, 32), 12: (DMA256, 256, 256), 13: (DMA256, 256, 192), 14: (DMA256, 256, 128)}
+UNTUNED = (0, 5, 11)      # conv() does not time these (0: code 4's 8 waves run the same tile better)
+# mspi_gemm_sp_fwd takes the LDS-DMA codes with a fixed BN (11 as 128 x 256): 128 x {128,64,96,192,256}, 256 x {256,192,128}
+SP_TILES = tuple(t for t, (kind, _, bn) in TILES.items() if kind >= DMA128 and bn)
+
+
+def _tiles(*kinds, all_cols=False):
+    return [t for t, (kind, _, bn) in TILES.items() if kind in kinds and t not in UNTUNED and (bn == 0) == all_cols]
+
+
+def gemm_kernel_name(code):
+    """Profiler name of the instantiation a variant code (mspi_conv_variant, mspi_gemm_sp_variant) stands for."""
+    kind, bm, bn, form = code // 10 ** 7, code // 10 ** 4 % 1000, code // 10 % 1000, code % 10
+    if kind in (REG4, REG8):
+        how = ("s" if form & 2 else "v4") + ("w8" if kind == REG8 else "")
+        return "conv_gemm<%d,%d,%s,%s>" % (bm, bn, how, "f16x3" if form & 1 else "f32")
+    return "conv_gemm<%d,%d,%s,f16x3>" % (bm, bn, "dma" if kind in (DMA128, DMA256) else "dma-presplit")
 
 
 W_BLOCKED = _os.environ.get("MSPI_W_BLOCKED", "1") != "0"      # A/B switch: blocked weights for the LDS-DMA kernels on fp32 activations
 
 
 def _sp_tiles(M):
-    return [t for t in SP_TILES if t < 12 or M >= 4096]
+    return [t for t in SP_TILES if TILES[t][0] != DMA256 or M >= 4096]
 
 
 def _conv_sp(x, pk, out, res, act, tile, sp_out):
@@ -502,17 +522,16 @@ def _conv_sp(x, pk, out, res, act, tile, sp_out):
                 "M=%d K=%d(1x%d) N=%d pre-split%s%s" % (M, pk.cin, pk.cin, pk.cout, " +res" if res is not None else "", " ->planes" if sp_out else "")) as tm:
         check(launch(choice), "mspi_gemm_sp_fwd")
         if Profiler.active is not None:
-            c = lib.mspi_conv_last_config()
-            tm.name = "conv_gemm<%d,%d,dma-presplit,f16x3>" % (c >> 16, (c >> 4) & 0xFFF)
+            tm.name = gemm_kernel_name(lib.mspi_gemm_sp_variant(C.byref(d), args[7]))
     return out
 
 
 def _conv_kernels(pk, d, M, rg, halo, gate):
-    cands = [1, 2, 3, 4]
+    cands = _tiles(REG4, REG8)
     if pk.prec == PREC_F16X3 and d.sC == 1 and d.C % 4 == 0:
-        cands += [6, 7, 9, 10] + ([8] if pk.cout_s <= 256 else [])
+        cands += _tiles(DMA128) + (_tiles(DMA128, all_cols=True) if pk.cout_s <= 256 else [])
         if M >= 16384:
-            cands += [12, 13, 14]        # 256-row / 8-wave form of the LDS-DMA kernel
+            cands += _tiles(DMA256)        # 256-row / 8-wave form of the LDS-DMA kernel
     if rg is not None:
         cands.append(THIN)
     if halo:
@@ -637,10 +656,7 @@ def conv(x, pk, out=None, res=None, gate=None, act=None, tile=None, sp_out=False
             elif choice >= SPLITK:
                 tm.name = "conv_gemm<64,64,splitk%d>" % (choice - SPLITK)
             else:
-                c = lib.mspi_conv_last_config()
-                tm.name = "conv_gemm<%d,%d,%s,%s>" % (c >> 16, (c >> 4) & 0xFFF,
-                                                      "dma" if c & 4 else ("s" if c & 1 else "v4") + ("w8" if c & 8 else ""),
-                                                      "f16x3" if (c >> 1) & 1 else "f32")
+                tm.name = gemm_kernel_name(lib.mspi_conv_variant(C.byref(d), xptr, args[4], 1))
     return out
 
 

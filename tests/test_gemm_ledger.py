@@ -468,6 +468,80 @@ def test_production_shapes_keep_their_kernels():
     assert [_conv_code(dict(readout, H=hw, W=hw)) for hw in (56, 28)] == [41280640, 41280640]      # deep_conv: DMA, BN 64
 
 
+def _old_profiler_name(c, presplit):
+    """The name engine.conv / engine._conv_sp built from the bitfield mspi_conv_last_config() returned, before the variant
+    code took its place: the same shifts, masks and format strings."""
+    if presplit:
+        return "conv_gemm<%d,%d,dma-presplit,f16x3>" % (c >> 16, (c >> 4) & 0xFFF)
+    return "conv_gemm<%d,%d,%s,%s>" % (c >> 16, (c >> 4) & 0xFFF,
+                                       "dma" if c & 4 else ("s" if c & 1 else "v4") + ("w8" if c & 8 else ""),
+                                       "f16x3" if (c >> 1) & 1 else "f32")
+
+
+def test_gemm_kernel_name_is_the_name_the_last_launch_bitfield_gave():
+    """engine.gemm_kernel_name(code) for every conv and pre-split ledger row against the old path restated: the bitfield
+    (BM << 16) | (BN << 4) | (8 if 8 waves) | (prec << 1) | (4 if LDS-DMA else 1 if scalar gather) the launches used to
+    leave behind, built from the row, decoded as engine.py decoded it.  Split-K (kind 3) is named from the kernel choice: GPU
+    test below."""
+    from mspi_amd import engine as E
+    for code, r in CONV_LEDGER.items():
+        kind, bm, bn = code // 10 ** 7, (code // 10 ** 4) % 1000, (code // 10) % 1000
+        if kind == 3:
+            continue
+        dma = kind in (4, 5)
+        scalar = r["layout"] == "ncdhw" or r["C"] % 4 != 0
+        w8 = kind == 2 or (dma and bm == 256)
+        c = (bm << 16) | (bn << 4) | (8 if w8 else 0) | (r["prec"] << 1) | (4 if dma else 1 if scalar else 0)
+        assert E.gemm_kernel_name(code) == _old_profiler_name(c, False), code
+    for code in SP_LEDGER:
+        bm, bn = (code // 10 ** 4) % 1000, (code // 10) % 1000
+        c = (bm << 16) | (bn << 4) | (8 if bm == 256 else 0) | (F16X3 << 1) | 4
+        assert E.gemm_kernel_name(code) == _old_profiler_name(c, True), code
+
+
+def test_engine_tiles_restate_the_library_table():
+    """engine.TILES (code -> kind, BM, BN) against the codes the library's own table gives the ledger rows: every tile code has
+    a row, and the pre-split codes are engine.SP_TILES with code 11 as 128 x 256."""
+    from mspi_amd import engine as E
+    seen = set()
+    for code, r in CONV_LEDGER.items():
+        kind, bm, bn = code // 10 ** 7, (code // 10 ** 4) % 1000, (code // 10) % 1000
+        if kind == 3 or r["tile"] < 0:
+            continue
+        want = E.TILES[r["tile"]]
+        assert (kind, bm) == want[:2] and (bn == want[2] or (want[2] == 0 and bn == (r["Cout"] + 31) // 32 * 32)), (code, want)
+        seen.add(r["tile"])
+    assert seen == set(E.TILES) == set(range(15))
+    sp = {row[6]: ((code // 10 ** 7) - 2, (code // 10 ** 4) % 1000, (code // 10) % 1000) for code, row in SP_LEDGER.items() if row[6] >= 0}
+    assert set(sp) == set(E.SP_TILES)
+    assert all(sp[t] == (E.TILES[t] if t != 11 else (E.DMA128, 128, 256)) for t in sp)
+
+
+def test_autotune_candidate_lists():
+    """engine._conv_kernels and engine._sp_tiles, built from engine.TILES, are the literal lists the autotuner has timed so far."""
+    from types import SimpleNamespace as NS
+    from mspi_amd import engine as E
+
+    def cands(prec, cout, M, sC=1, Cc=20):
+        return E._conv_kernels(NS(prec=prec, cout_s=cout, ldw=32), NS(sC=sC, C=Cc), M, None, False, None)
+
+    assert cands(F32, 192, 378) == [1, 2, 3, 4]
+    assert cands(F16X3, 192, 378) == [1, 2, 3, 4, 6, 7, 9, 10, 8]
+    assert cands(F16X3, 192, 16383) == [1, 2, 3, 4, 6, 7, 9, 10, 8]
+    assert cands(F16X3, 192, 16384) == [1, 2, 3, 4, 6, 7, 9, 10, 8, 12, 13, 14]
+    assert cands(F16X3, 256, 378) == [1, 2, 3, 4, 6, 7, 9, 10, 8]
+    assert cands(F16X3, 320, 378) == [1, 2, 3, 4, 6, 7, 9, 10]
+    assert cands(F16X3, 320, 16384) == [1, 2, 3, 4, 6, 7, 9, 10, 12, 13, 14]
+    assert cands(F16X3, 192, 16384, sC=63) == [1, 2, 3, 4] and cands(F16X3, 192, 16384, Cc=6) == [1, 2, 3, 4]      # scalar gather
+    assert E._sp_tiles(4095) == [6, 7, 9, 10, 11]
+    assert E._sp_tiles(4096) == [6, 7, 9, 10, 11, 12, 13, 14]
+    assert E.SP_TILES == (6, 7, 9, 10, 11, 12, 13, 14) and (E.THIN, E.SPLITK, E.HALO) == (100, 200, 300)
+    # extra candidates keep their places behind the tile codes
+    pk, d = NS(prec=F16X3, cout_s=76, ldw=32 * 32), NS(sC=1, C=20)
+    assert E._conv_kernels(pk, d, 378, object(), True, None) == [1, 2, 3, 4, 6, 7, 9, 10, 8, E.THIN, E.HALO] + \
+        ([E.SPLITK + 2, E.SPLITK + 4] if E.SPLITK_ENABLED else [])
+
+
 # ------------------------------------------------------------------------------------------------------------ GPU tests
 def _act64(v, a):
     return (v, v.clamp_min(0), F.gelu(v), torch.sigmoid(v), v * torch.sigmoid(v))[a]
@@ -780,4 +854,64 @@ def test_x3d_ca_ledger_kernel_vs_fp64(dev, code):
     _rel_close(y.as_rows()[:, :Cx], y_ref, 1e-5, "x3d_ca %d y" % code)
     _rel_close(t.as_rows()[:, :D], t_ref, 1e-5, "x3d_ca %d t" % code)
     torch.cuda.synchronize()
+    assert not E.range_flag()
+
+
+@pytest.mark.gpu
+def test_profiler_names_of_forced_launches(dev):
+    """The names engine.Profiler records for one forced launch of each naming path, on the ledger's small geometries
+    (M = 378): register tiles, LDS-DMA tiles and pre-split tiles through engine.gemm_kernel_name and the variant queries,
+    THIN / split-K / HALO from the kernel choice.  bench.py's roofline line and the tools key on these strings."""
+    from mspi_amd import engine as E
+    lib = E._lib.load()
+    g = torch.Generator().manual_seed(7)
+
+    def conv_row(r, tile, want=None):
+        """One E.conv launch of ledger-style row r with the forced kernel choice; returns (recorded names, pack, input)."""
+        x = torch.randn(r["N"], r["C"], r["T"], r["H"], r["W"], generator=g)
+        w = torch.randn(r["Cout"], r["C"], *r["k"], generator=g) / math.sqrt(r["C"] * math.prod(r["k"]))
+        pk = E.pack_conv(w, torch.randn(r["Cout"], generator=g), None, r["s"], r["p"], device=dev, prec=r["prec"])
+        if r["layout"] == "ncdhw":
+            xin = x.to(dev)
+        else:
+            ld = _ldx(r)
+            buf = torch.zeros(r["N"] * r["T"] * r["H"] * r["W"] * ld, device=dev)
+            c0 = 8 if r["layout"] == "slab" else 0
+            buf.view(-1, ld)[:, c0:c0 + r["C"]] = x.permute(0, 2, 3, 4, 1).reshape(-1, r["C"]).to(dev)
+            xin = E.CL(buf, c0, r["N"], r["T"], r["H"], r["W"], r["C"], ld)
+        with E.Profiler() as prof:
+            E.conv(xin, pk, tile=tile)
+        torch.cuda.synchronize()
+        names = [rec[0] for rec in prof.records]
+        if want is not None:
+            assert names == [want], (tile, names)
+        return names, pk, xin
+
+    _guard(E, dev)
+    conv_row(CONV_LEDGER[10640641], 3, "conv_gemm<64,64,v4,f16x3>")               # f16x3 slab row
+    conv_row(CONV_LEDGER[21281282], 4, "conv_gemm<128,128,sw8,f32>")              # raw NCDHW f32 row
+    conv_row(CONV_LEDGER[41280641], 7, "conv_gemm<128,64,dma,f16x3>")             # LDS-DMA dense rows
+    conv_row(_row(DENSE, 20, 140, "slab", F16X3, 14), 14, "conv_gemm<256,128,dma,f16x3>")
+    conv_row(CONV_LEDGER[30640640], E.SPLITK + 2, "conv_gemm<64,64,splitk2>")
+    names, pk, _ = conv_row(_row(DENSE, 20, 76, "cl", F16X3, -1), E.THIN)
+    assert pk.thin is not None and names == ["rowgemm<%d,f16x3>" % E.rowgemm_ksb(pk.cin_s)], names
+    # the smallest shape mspi_conv_halo_supported accepts: one output position, 32 channels, (1,3,3)
+    r = _row(((1, 3, 3), (1, 1, 1), (0, 1, 1), (1, 1, 1, 1)), 32, 4, "cl", F16X3, -1)
+    names, pk, xin = conv_row(r, E.HALO)
+    d = _conv_desc(r)
+    d.w_scale, d.w_blocked = pk.w_scale, E.sp_weights(pk).data_ptr()
+    v = lib.mspi_conv_halo_variant(C.byref(d), xin.ptr)
+    assert v > 0 and names == ["conv_halo<%d,%d,f16x3>" % (v // 1000, v % 1000)], (v, names)
+    # pre-split planes in: tile 6 with fp32 rows out, tile 13 with planes out
+    for code, want in ((61281280, "conv_gemm<128,128,dma-presplit,f16x3>"), (72561921, "conv_gemm<256,192,dma-presplit,f16x3>")):
+        N, T, H, W, K, Co, tile = SP_LEDGER[code]
+        pk = E.pack_conv(torch.randn(Co, K, generator=g) / math.sqrt(K), torch.randn(Co, generator=g), device=dev, prec=F16X3)
+        xd = torch.randn(N * T * H * W, K, generator=g).to(dev)
+        xs = E.alloc_sp(N, T, H, W, K, dev)
+        E.check(lib.mspi_split_planes_fwd(xd.data_ptr(), K, xd.shape[0], K, xs.ptr, xs.ld, xs.plane, E._stream()), "mspi_split_planes_fwd")
+        with E.Profiler() as prof:
+            out = E.conv(xs, pk, tile=tile, sp_out=code % 10 == 1)
+        torch.cuda.synchronize()
+        assert isinstance(out, E.SP) == (code % 10 == 1)
+        assert [rec[0] for rec in prof.records] == [want], (code, prof.records)
     assert not E.range_flag()
