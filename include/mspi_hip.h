@@ -228,7 +228,7 @@ int mspi_layernorm_variant(int32_t C, int32_t planes_out);
  * Fused multi-head attention (flash style, MFMA, online softmax, fp32 in / fp32 accumulate):
  *   o[b,h,i,:] = softmax_j( scale * q[b,h,i,:] . k[b,h,j,:] + biasT[h,j,i] + maskT[b % nmask,j,i] ) v[b,h,j,:] (+ res)
  * q/k/v/o (and res, with o's strides) are addressed as base + b*sB + h*sH + token*sT + d (d contiguous).
- * D = head dim of q/k, Dv = head dim of v/o; (D,Dv) in {(32,32),(64,64),(96,96),(128,128),(128,96),(144,96),(160,96)}.
+ * D = head dim of q/k, Dv = head dim of v/o; the instantiated pairs are listed at MspiAttnDesc.
  * biasT / maskT (optional) are stored key-major ([.][Nk][Nq]).
  * A non-finite stored output sets the status word (mspi_set_status_word), as the GEMM epilogues do; padded query rows and
  * key tiles never do.
@@ -240,6 +240,8 @@ int mspi_layernorm_variant(int32_t C, int32_t planes_out);
  * pooling as `res`), backbones/video_swin_transformer.py:169-187 (window attention, bias table + shift mask).
  * ------------------------------------------------------------------------------------ */
 typedef struct MspiAttnDesc {
+  /* (D, Dv) in {(32,32),(64,64),(96,96),(128,128),(128,96),(144,96),(160,96)} (kAttnPairs in csrc/attn.hip); any other pair is
+   * refused with this list by mspi_attn_fwd / mspi_attn_fwd_ws and answered with -1 by mspi_attn_variant */
   int32_t B, Hh, Nq, Nk, D, Dv, nmask, nwin;
   int64_t q_sB, q_sH, q_sT;
   int64_t k_sB, k_sH, k_sT;
@@ -260,7 +262,8 @@ int mspi_attn_fwd(const MspiAttnDesc* d, const float* q, const float* k, const f
  * Few-query shapes (fewer than 256 query tiles over all heads, at least 24 key tiles; no bias, mask or token index) are
  * additionally split along the keys: up to 8 workgroups per query tile each walk a slice of the key tiles and a third
  * launch merges their (O, running max, running sum) in fixed order -- deterministic, equal to the one-pass result up to
- * fp32 rounding of the merge; the workspace size accounts for the partial results.  MSPI_ATTN_KSPLIT=0 switches it off. */
+ * fp32 rounding of the merge; the workspace size accounts for the partial results.  MSPI_ATTN_KSPLIT=0 switches it off.
+ * mspi_attn_ws_bytes does not look at the pair (D, Dv); the launch refuses the pairs that are not at MspiAttnDesc. */
 size_t mspi_attn_ws_bytes(const MspiAttnDesc* d);
 int mspi_attn_fwd_ws(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
                      const float* biasT, const float* maskT, const int32_t* tok_idx, float* o, void* workspace,
@@ -271,7 +274,7 @@ int mspi_attn_fwd_ws(const MspiAttnDesc* d, const float* q, const float* k, cons
  *   kind * 10000000 + D * 10000 + Dv * 10 + (1 if the key split's merge pass runs)
  * kind 1 = fp32 (attn_kernel<D, Dv>), 2 = f16x3 without planes (attn_f16x3_kernel<D, Dv>), 3 = f16x3 on prefetched
  * planes (attn_f16x3_kernel<D, Dv, true, true>), 4 = the same without prefetch (<D, Dv, true, false>, MSPI_ATTN_PF=0),
- * 5 = software pipeline (attn_pipe_kernel<D, Dv>); -1 = (D, Dv) or prec not instantiated.
+ * 5 = software pipeline (attn_pipe_kernel<D, Dv>); -1 = prec, or a (D, Dv) that is not at MspiAttnDesc, not instantiated.
  * mspi_attn_fwd / mspi_attn_fwd_ws select their kernels by this same function. */
 int mspi_attn_variant(const MspiAttnDesc* d, int32_t has_bias, int32_t has_mask, int32_t has_tok, int32_t has_ws);
 

@@ -15,6 +15,8 @@
 // fragment reads conflict-free ds_read_b32.
 #include "common.h"
 
+#include <string>
+
 namespace mspi {
 
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -45,6 +47,56 @@ struct AttnArgs {
   int* status;         // range guard (common.h, report_nonfinite): set when a stored output is inf / NaN
 };
 
+// Where a thread works: sequence b and head h of its workgroup and the query of its lane (wave w of a workgroup owns queries
+// 32 w .. 32 w + 31 of the workgroup's 128, both lane halves the same query; the plane kernel has no queries and ignores q).
+// Windowed sequences (Swin): b = sample * nwin + win; rows are looked up, so the cyclic shift, the window partition and their
+// inverses are pure index arithmetic -- no gather / scatter pass over the activations.  TOK = false: the kernel is never
+// launched with a token index.
+struct AttnCoord {
+  int b, h, q, sample, qrow;   // qrow: the query's row in its sample (0 for padded queries)
+  bool qok;                    // q < Nq
+  const int* tix;              // token index of this window, or null
+  // offset of (sample, head) in q, k, v or o
+  __device__ __forceinline__ long head(long sB, long sH) const { return (long)sample * sB + (long)h * sH; }
+};
+
+template <bool TOK = true>
+__device__ __forceinline__ AttnCoord attn_coord(const AttnArgs p) {
+  AttnCoord c;
+  c.b = blockIdx.y / p.Hh;
+  c.h = blockIdx.y % p.Hh;
+  c.q = blockIdx.x * 128 + (threadIdx.x >> 6) * 32 + (threadIdx.x & 31);
+  c.qok = c.q < p.Nq;
+  c.sample = TOK && p.tok_idx ? c.b / p.nwin : c.b;
+  c.tix = TOK && p.tok_idx ? p.tok_idx + (long)(c.b % p.nwin) * p.Nk : nullptr;
+  c.qrow = c.qok ? (c.tix ? c.tix[c.q] : c.q) : 0;
+  return c;
+}
+
+// Epilogue of one query row: O^T accumulators times inv (+ res), range guard, 16-byte stores at o + oo.  Lane half lh holds,
+// in registers 4g .. 4g+3 of tile t, the 4 consecutive d = t*32 + 8g + 4*lh + (0..3).  Takes plain values and pointers, not
+// a reference to the kernel's argument struct (that form made attn_pipe_kernel and attn_f16x3_kernel<.., true, ..> larger).
+template <int NT>
+__device__ __forceinline__ void attn_store_row(const v16f (&acc)[NT], float inv, int lh, const float* res, float* o, long oo,
+                                               int* status) {
+  bool bad = false;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      float4 o4 = make_float4(acc[t][4 * g] * inv, acc[t][4 * g + 1] * inv, acc[t][4 * g + 2] * inv,
+                              acc[t][4 * g + 3] * inv);
+      const int dd = t * 32 + 8 * g + 4 * lh;
+      if (res) {
+        const float4 rr = *reinterpret_cast<const float4*>(res + oo + dd);
+        o4.x += rr.x; o4.y += rr.y; o4.z += rr.z; o4.w += rr.w;
+      }
+      bad |= nonfinite4(o4);
+      *reinterpret_cast<float4*>(o + oo + dd) = o4;
+    }
+  report_nonfinite(status, bad);
+}
+
 // D = head dim of Q/K (the contraction of S), DV = head dim of V / O.  They differ for MViT, whose decomposed
 // relative-position terms ride along as extra Q/K columns (mvit_aug_kernel below).
 template <int D, int DV>
@@ -59,11 +111,10 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
+  // this kernel keeps its own copy of attn_coord: through the shared function <32, 32> and <64, 64> need one more scalar register
   const int b = blockIdx.y / p.Hh, h = blockIdx.y % p.Hh;
   const int q = blockIdx.x * 128 + wave * 32 + li;
   const bool qok = q < p.Nq;
-  // windowed sequences (Swin): b = sample * nwin + win; rows are looked up, so the cyclic shift, the window
-  // partition and their inverses are pure index arithmetic -- no gather / scatter pass over the activations
   const int sample = p.tok_idx ? b / p.nwin : b;
   const int* tix = p.tok_idx ? p.tok_idx + (long)(b % p.nwin) * p.Nk : nullptr;
   const int qrow = qok ? (tix ? tix[q] : q) : 0;
@@ -170,27 +221,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs p) {
     }
   }
 
-  if (qok) {      // padded query rows (q >= Nq) store nothing and are never flagged
-    const float inv = 1.f / l_run;
-    const long oo = (long)sample * p.o_sB + (long)h * p.o_sH + (long)qrow * p.o_sT;
-    bool bad = false;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        // registers 4g..4g+3 are 4 consecutive d: d = t*32 + 8g + 4*lh + (0..3)
-        float4 o4 = make_float4(acc[t][4 * g] * inv, acc[t][4 * g + 1] * inv, acc[t][4 * g + 2] * inv,
-                                acc[t][4 * g + 3] * inv);
-        const int dd = t * 32 + 8 * g + 4 * lh;
-        if (p.res) {
-          const float4 rr = *reinterpret_cast<const float4*>(p.res + oo + dd);
-          o4.x += rr.x; o4.y += rr.y; o4.z += rr.z; o4.w += rr.w;
-        }
-        bad |= nonfinite4(o4);
-        *reinterpret_cast<float4*>(p.o + oo + dd) = o4;
-      }
-    report_nonfinite(p.status, bad);
-  }
+  if (qok)      // padded query rows (q >= Nq) store nothing and are never flagged
+    attn_store_row<NT>(acc, 1.f / l_run, lh, p.res, p.o, (long)sample * p.o_sB + (long)h * p.o_sH + (long)qrow * p.o_sT, p.status);
 }
 
 // ------------------------------------------------------------------ the same attention on the f16 matrix pipe
@@ -222,56 +254,62 @@ __device__ __forceinline__ void split4(const float4 v, v4h& hi, v4h& lo) {
 #ifndef MSPI_ATT_PV_DROP
 #define MSPI_ATT_PV_DROP 0
 #endif
-constexpr float ATT_KSC = 16.f, ATT_VSC = 16.f, ATT_PSC = 1024.f;
+// Power-of-two operand scales (exact; undone on the fp32 side).  The lo half of a split value is ~2^-12 of it, and
+// f16 loses precision below 2^-14 (subnormals; the matrix pipe may flush them): q*scale ~ 0.1 and p <= 1 would keep
+// only their hi halves.  Scaled, every operand of ordinary magnitude has a NORMAL lo half.
+constexpr float ATT_QSC = 64.f, ATT_KSC = 16.f, ATT_VSC = 16.f, ATT_PSC = 1024.f;
 
-// K and V of every (sequence, head) split ONCE into the f16 hi/lo planes the attention kernel stages: every query tile of
-// that head (196 workgroups at Nq = 25088) used to redo this split on its own copy -- ~200 VALU instructions per thread and
-// 32-key step, beside ~60 MFMAs.  One workgroup per 32-key tile; same arithmetic as the in-kernel staging, so the planes
-// hold bit for bit what attn_f16x3_kernel<.., false> puts into LDS.
-// IMG: the planes are written as per-tile LDS IMAGES -- for each (sequence, head) and 32-key tile the K tile [hi, lo][32][D + 8]
-// and the V^T tile [hi, lo][DV][36] exactly as attn_pipe_kernel keeps them in LDS (row pads included, the V image rounded up to
-// a multiple of 1 KB), each one contiguous, so that a tile is staged by plain 1-KB LDS-DMA pieces.
-template <int D, int DV> struct AttnImg {
-  static constexpr int KP = D + 8, VP = 36;
-  static constexpr int KTI = 2 * 32 * KP;                               // halves per K image (a multiple of 512: whole KB)
-  static constexpr int VTI = (2 * DV * VP * 2 + 1023) / 1024 * 512;     // halves per V image, rounded up to whole KB
-};
+// Q^T fragments (B operand of S^T = K . Q^T) of the query row at qp: lane (q, half lh) holds d = 16 s + 8 lh + e, times
+// ATT_QSC (the softmax scale is applied to S in fp32, so this scaling stays an exact power of two), split hi / lo.
+template <int NS>
+__device__ __forceinline__ void attn_load_q(const float* qp, bool qok, int lh, v8h (&qh)[NS], v8h (&ql)[NS]) {
+  qp += 8 * lh;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    float4 a = *reinterpret_cast<const float4*>(qp + 16 * s);
+    float4 c = *reinterpret_cast<const float4*>(qp + 16 * s + 4);
+    if (!qok) { a = make_float4(0.f, 0.f, 0.f, 0.f); c = a; }
+    const float qs = ATT_QSC;
+    const float f[8] = {a.x * qs, a.y * qs, a.z * qs, a.w * qs, c.x * qs, c.y * qs, c.z * qs, c.w * qs};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      _Float16 hh, ll;
+      split_f16(f[e], hh, ll);
+      qh[s][e] = hh; ql[s][e] = ll;
+    }
+  }
+}
 
-template <int D, int DV, bool IMG = false>
-__global__ __launch_bounds__(256) void attn_kv_planes_kernel(const AttnArgs p) {
+// One 32-key tile of K and V (keys k0 .. k0 + 31 of the head at kb / vb, rows through the token index tix if there is one)
+// times ATT_KSC / ATT_VSC, split into f16 hi / lo planes; keys beyond Nk give zeros.  The tile's keys become rows dkey0 .. + 31
+// of Kh / Kl (kpitch halves apart) and columns dkey0 .. + 31 of the TRANSPOSED Vh / Vl (one row per d, vpitch apart): dkey0 = k0
+// in whole planes, 0 in a tile of its own.
+// The destination is LDS (attn_f16x3_kernel without planes) or the workspace planes (attn_kv_planes_kernel), so the two
+// hold the same bits.
+//   K: thread -> (key row, 4 d): two 8-B plane writes;  V: thread -> (key pair fastest, 4 d): 4-B writes Vt[d][2kp .. 2kp+1]
+template <int D, int DV>
+__device__ __forceinline__ void attn_split_kv_tile(const float* kb, long k_sT, const float* vb, long v_sT, const int* tix, int k0,
+                                                   int Nk, int dkey0, _Float16* Kh, _Float16* Kl, long kpitch, _Float16* Vh,
+                                                   _Float16* Vl, long vpitch) {
   const int tid = threadIdx.x;
-  const int b = blockIdx.y / p.Hh, h = blockIdx.y % p.Hh;
-  const int k0 = blockIdx.x * 32;
-  const int sample = p.tok_idx ? b / p.nwin : b;
-  const int* tix = p.tok_idx ? p.tok_idx + (long)(b % p.nwin) * p.Nk : nullptr;
-  const float* kb = p.k + (long)sample * p.k_sB + (long)h * p.k_sH;
-  const float* vb = p.v + (long)sample * p.v_sB + (long)h * p.v_sH;
-  typedef AttnImg<D, DV> I;
-  const long tile = (long)blockIdx.y * (p.Nkp >> 5) + blockIdx.x;
-  // plain layout: planes [hi, lo][Nkp][D] and [hi, lo][DV][Nkp] per (sequence, head); row / column index includes k0
-  _Float16* Kh = IMG ? p.kp + tile * I::KTI - (long)k0 * I::KP : p.kp + (long)blockIdx.y * 2 * p.Nkp * D;
-  _Float16* Kl = IMG ? Kh + 32 * I::KP : Kh + (long)p.Nkp * D;
-  _Float16* Vh = IMG ? p.vp + tile * I::VTI - k0 : p.vp + (long)blockIdx.y * 2 * DV * p.Nkp;
-  _Float16* Vl = IMG ? Vh + DV * I::VP : Vh + (long)DV * p.Nkp;
-  const long kpitch = IMG ? I::KP : D, vpitch = IMG ? I::VP : p.Nkp;
   for (int idx = tid; idx < 32 * (D / 4); idx += 256) {
     const int row = idx / (D / 4), c4 = idx - row * (D / 4);
-    const bool ok = k0 + row < p.Nk;
+    const bool ok = k0 + row < Nk;
     const int kr = ok ? (tix ? tix[k0 + row] : k0 + row) : 0;
-    float4 kv = *reinterpret_cast<const float4*>(kb + (long)kr * p.k_sT + c4 * 4);
+    float4 kv = *reinterpret_cast<const float4*>(kb + (long)kr * k_sT + c4 * 4);
     kv = ok ? make_float4(kv.x * ATT_KSC, kv.y * ATT_KSC, kv.z * ATT_KSC, kv.w * ATT_KSC) : make_float4(0.f, 0.f, 0.f, 0.f);
     v4h hi, lo;
     split4(kv, hi, lo);
-    *reinterpret_cast<v4h*>(&Kh[(long)(k0 + row) * kpitch + c4 * 4]) = hi;
-    *reinterpret_cast<v4h*>(&Kl[(long)(k0 + row) * kpitch + c4 * 4]) = lo;
+    *reinterpret_cast<v4h*>(&Kh[(long)(dkey0 + row) * kpitch + c4 * 4]) = hi;
+    *reinterpret_cast<v4h*>(&Kl[(long)(dkey0 + row) * kpitch + c4 * 4]) = lo;
   }
   for (int idx = tid; idx < 16 * (DV / 4); idx += 256) {
     const int kp = idx & 15, c4 = idx >> 4;
-    const bool ok0 = k0 + 2 * kp < p.Nk, ok1 = k0 + 2 * kp + 1 < p.Nk;
+    const bool ok0 = k0 + 2 * kp < Nk, ok1 = k0 + 2 * kp + 1 < Nk;
     const int r0 = ok0 ? (tix ? tix[k0 + 2 * kp] : k0 + 2 * kp) : 0;
     const int r1 = ok1 ? (tix ? tix[k0 + 2 * kp + 1] : k0 + 2 * kp + 1) : 0;
-    float4 v0 = *reinterpret_cast<const float4*>(vb + (long)r0 * p.v_sT + c4 * 4);
-    float4 v1 = *reinterpret_cast<const float4*>(vb + (long)r1 * p.v_sT + c4 * 4);
+    float4 v0 = *reinterpret_cast<const float4*>(vb + (long)r0 * v_sT + c4 * 4);
+    float4 v1 = *reinterpret_cast<const float4*>(vb + (long)r1 * v_sT + c4 * 4);
     v0 = ok0 ? make_float4(v0.x * ATT_VSC, v0.y * ATT_VSC, v0.z * ATT_VSC, v0.w * ATT_VSC) : make_float4(0.f, 0.f, 0.f, 0.f);
     v1 = ok1 ? make_float4(v1.x * ATT_VSC, v1.y * ATT_VSC, v1.z * ATT_VSC, v1.w * ATT_VSC) : make_float4(0.f, 0.f, 0.f, 0.f);
     v4h h0, l0, h1, l1;
@@ -283,22 +321,64 @@ __global__ __launch_bounds__(256) void attn_kv_planes_kernel(const AttnArgs p) {
       v2h ph, pl;
       ph[0] = h0[j]; ph[1] = h1[j];
       pl[0] = l0[j]; pl[1] = l1[j];
-      *reinterpret_cast<v2h*>(&Vh[(long)(c4 * 4 + j) * vpitch + k0 + 2 * kp]) = ph;
-      *reinterpret_cast<v2h*>(&Vl[(long)(c4 * 4 + j) * vpitch + k0 + 2 * kp]) = pl;
+      *reinterpret_cast<v2h*>(&Vh[(long)(c4 * 4 + j) * vpitch + dkey0 + 2 * kp]) = ph;
+      *reinterpret_cast<v2h*>(&Vl[(long)(c4 * 4 + j) * vpitch + dkey0 + 2 * kp]) = pl;
     }
   }
 }
 
+// Key split: slice blockIdx.z leaves its unnormalised O^T, running maximum and running sum of query q for attn_merge_kernel.
+template <int NT, int DV>
+__device__ __forceinline__ void attn_store_partial(const v16f (&acc)[NT], float m_run, float l_run, int lh, float* part_o,
+                                                   float* part_ml, int Nq, int q) {
+  const long pr = ((long)blockIdx.z * gridDim.y + blockIdx.y) * Nq + q;
+  if (lh == 0) *reinterpret_cast<float2*>(part_ml + pr * 2) = make_float2(m_run, l_run);
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      *reinterpret_cast<float4*>(part_o + pr * DV + t * 32 + 8 * g + 4 * lh) =
+          make_float4(acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]);
+}
+
+// K and V of every (sequence, head) split ONCE into the f16 hi/lo planes the attention kernel stages: every query tile of
+// that head (196 workgroups at Nq = 25088) used to redo this split on its own copy -- ~200 VALU instructions per thread and
+// 32-key step, beside ~60 MFMAs.  One workgroup per 32-key tile, split by the function attn_f16x3_kernel<.., false> stages
+// with (attn_split_kv_tile), so the planes hold bit for bit what that kernel puts into LDS.
+// IMG: the planes are written as per-tile LDS IMAGES -- for each (sequence, head) and 32-key tile the K tile [hi, lo][32][D + 8]
+// and the V^T tile [hi, lo][DV][36] exactly as attn_pipe_kernel keeps them in LDS (row pads included, the V image rounded up to
+// a multiple of 1 KB), each one contiguous, so that a tile is staged by plain 1-KB LDS-DMA pieces.
+constexpr int ATT_KPAD = 8, ATT_VP = 36;      // K rows are D + 8 halves, V^T rows 32 keys + 4
+constexpr int attn_img_k(int D) { return 2 * 32 * (D + ATT_KPAD); }                          // halves per K image (a multiple of 512: whole KB)
+constexpr int attn_img_v(int DV) { return (2 * DV * ATT_VP * 2 + 1023) / 1024 * 512; }       // halves per V image, rounded up to whole KB
+template <int D, int DV> struct AttnImg {      // the host sizes the workspace by the same two functions (attn_ws_layout)
+  static constexpr int KP = D + ATT_KPAD, VP = ATT_VP;
+  static constexpr int KTI = attn_img_k(D), VTI = attn_img_v(DV);
+};
+
+template <int D, int DV, bool IMG = false>
+__global__ __launch_bounds__(256) void attn_kv_planes_kernel(const AttnArgs p) {
+  typedef AttnImg<D, DV> I;
+  const AttnCoord c = attn_coord(p);
+  const int k0 = blockIdx.x * 32;
+  const long tile = (long)blockIdx.y * (p.Nkp >> 5) + blockIdx.x;
+  // plain layout: planes [hi, lo][Nkp][D] and [hi, lo][DV][Nkp] per (sequence, head), this tile at key k0; an image is
+  // addressed the same way, from k0 rows / columns before its start
+  _Float16* Kh = IMG ? p.kp + tile * I::KTI - (long)k0 * I::KP : p.kp + (long)blockIdx.y * 2 * p.Nkp * D;
+  _Float16* Kl = IMG ? Kh + 32 * I::KP : Kh + (long)p.Nkp * D;
+  _Float16* Vh = IMG ? p.vp + tile * I::VTI - k0 : p.vp + (long)blockIdx.y * 2 * DV * p.Nkp;
+  _Float16* Vl = IMG ? Vh + DV * I::VP : Vh + (long)DV * p.Nkp;
+  attn_split_kv_tile<D, DV>(p.k + c.head(p.k_sB, p.k_sH), p.k_sT, p.v + c.head(p.v_sB, p.v_sH), p.v_sT, c.tix, k0, p.Nk, k0, Kh, Kl,
+                            IMG ? I::KP : D, Vh, Vl, IMG ? I::VP : p.Nkp);
+}
+
 template <int D, int DV, bool PL = false, bool PF = false>
 __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const AttnArgs p) {
-  constexpr int KP = D + 8;     // K plane row pitch (halves)
-  constexpr int VP = 36;        // Vt plane row pitch (halves): 32 keys + 4
-  constexpr int NS = D / 16;    // k16 steps of S
-  constexpr int NT = DV / 32;   // 32-wide output tiles along d
-  // Power-of-two operand scales (exact; undone on the fp32 side).  The lo half of a split value is ~2^-12 of it, and
-  // f16 loses precision below 2^-14 (subnormals; the matrix pipe may flush them): q*scale ~ 0.1 and p <= 1 would keep
-  // only their hi halves.  Scaled, every operand of ordinary magnitude has a NORMAL lo half.
-  constexpr float QSC = 64.f, KSC = ATT_KSC, PSC = ATT_PSC, VSC = ATT_VSC;
+  constexpr int KP = D + ATT_KPAD;     // K plane row pitch (halves)
+  constexpr int VP = ATT_VP;           // Vt plane row pitch (halves): 32 keys + 4
+  constexpr int NS = D / 16;           // k16 steps of S
+  constexpr int NT = DV / 32;          // 32-wide output tiles along d
+  constexpr float QSC = ATT_QSC, KSC = ATT_KSC, PSC = ATT_PSC, VSC = ATT_VSC;
   // With prefetched planes (PL && PF) the K / V tiles are DOUBLE-buffered in LDS: tile t+1 is written (from the registers the
   // prefetch filled) behind tile t's MFMAs, so a key tile costs one barrier, not two, and no wave waits for staging.
   constexpr int TILE = 2 * 32 * KP + 2 * DV * VP;
@@ -308,34 +388,13 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const AttnArgs p) {
     Kh = smem + bsel * TILE; Kl = Kh + 32 * KP; Vh = Kh + 2 * 32 * KP; Vl = Vh + DV * VP;
   };
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int li = lane & 31, lh = lane >> 5;
-  const int b = blockIdx.y / p.Hh, h = blockIdx.y % p.Hh;
-  const int q = blockIdx.x * 128 + wave * 32 + li;
-  const bool qok = q < p.Nq;
-  const int sample = p.tok_idx ? b / p.nwin : b;
-  const int* tix = p.tok_idx ? p.tok_idx + (long)(b % p.nwin) * p.Nk : nullptr;
-  const int qrow = qok ? (tix ? tix[q] : q) : 0;
+  const AttnCoord c = attn_coord(p);
+  const bool qok = c.qok;
 
-  // Q^T fragments (B operand): lane (q, half) holds d = 16 s + 8 half + e
   v8h qh[NS], ql[NS];
-  {
-    const float* qp = p.q + (long)sample * p.q_sB + (long)h * p.q_sH + (long)qrow * p.q_sT + 8 * lh;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      float4 a = *reinterpret_cast<const float4*>(qp + 16 * s);
-      float4 c = *reinterpret_cast<const float4*>(qp + 16 * s + 4);
-      if (!qok) { a = make_float4(0.f, 0.f, 0.f, 0.f); c = a; }
-      const float qs = QSC;   // the softmax scale is applied to S in fp32, so this scaling stays an exact power of two
-      const float f[8] = {a.x * qs, a.y * qs, a.z * qs, a.w * qs, c.x * qs, c.y * qs, c.z * qs, c.w * qs};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        _Float16 hh, ll;
-        split_f16(f[e], hh, ll);
-        qh[s][e] = hh; ql[s][e] = ll;
-      }
-    }
-  }
+  attn_load_q<NS>(p.q + c.head(p.q_sB, p.q_sH) + (long)c.qrow * p.q_sT, qok, lh, qh, ql);
 
   v16f acc[NT];
 #pragma unroll
@@ -344,8 +403,8 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const AttnArgs p) {
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
 
-  const float* kb = p.k + (long)sample * p.k_sB + (long)h * p.k_sH;
-  const float* vb = p.v + (long)sample * p.v_sB + (long)h * p.v_sH;
+  const float* kb = p.k + c.head(p.k_sB, p.k_sH);
+  const float* vb = p.v + c.head(p.v_sB, p.v_sH);
 
   constexpr int PFK = PL ? (32 * (D / 8) + 255) / 256 : 1, PFV = PL ? (DV * 4 + 255) / 256 : 1;
   uint4 pf_kh[PFK], pf_kl[PFK], pf_vh[PFV], pf_vl[PFV];
@@ -416,41 +475,7 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const AttnArgs p) {
     if (!(PL && PF)) __syncthreads();  // previous tile fully consumed
     if (PL && !PF) prefetch(k0);
     if (PL && !PF) stage_write(smem);
-    // K: thread -> (key row, 4 d): two 8-B plane writes
-    for (int idx = tid; !PL && idx < 32 * (D / 4); idx += 256) {
-      const int row = idx / (D / 4), c4 = idx - row * (D / 4);
-      const bool ok = k0 + row < p.Nk;
-      const int kr = ok ? (tix ? tix[k0 + row] : k0 + row) : 0;
-      float4 kv = *reinterpret_cast<const float4*>(kb + (long)kr * p.k_sT + c4 * 4);
-      kv = ok ? make_float4(kv.x * KSC, kv.y * KSC, kv.z * KSC, kv.w * KSC) : make_float4(0.f, 0.f, 0.f, 0.f);
-      v4h hi, lo;
-      split4(kv, hi, lo);
-      *reinterpret_cast<v4h*>(&Kh[row * KP + c4 * 4]) = hi;
-      *reinterpret_cast<v4h*>(&Kl[row * KP + c4 * 4]) = lo;
-    }
-    // V, transposed: thread -> (key pair fastest, 4 d): 4-B writes Vt[d][2kp .. 2kp+1]
-    for (int idx = tid; !PL && idx < 16 * (DV / 4); idx += 256) {
-      const int kp = idx & 15, c4 = idx >> 4;
-      const bool ok0 = k0 + 2 * kp < p.Nk, ok1 = k0 + 2 * kp + 1 < p.Nk;
-      const int r0 = ok0 ? (tix ? tix[k0 + 2 * kp] : k0 + 2 * kp) : 0;
-      const int r1 = ok1 ? (tix ? tix[k0 + 2 * kp + 1] : k0 + 2 * kp + 1) : 0;
-      float4 v0 = *reinterpret_cast<const float4*>(vb + (long)r0 * p.v_sT + c4 * 4);
-      float4 v1 = *reinterpret_cast<const float4*>(vb + (long)r1 * p.v_sT + c4 * 4);
-      v0 = ok0 ? make_float4(v0.x * VSC, v0.y * VSC, v0.z * VSC, v0.w * VSC) : make_float4(0.f, 0.f, 0.f, 0.f);
-      v1 = ok1 ? make_float4(v1.x * VSC, v1.y * VSC, v1.z * VSC, v1.w * VSC) : make_float4(0.f, 0.f, 0.f, 0.f);
-      v4h h0, l0, h1, l1;
-      split4(v0, h0, l0);
-      split4(v1, h1, l1);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        typedef _Float16 v2h __attribute__((ext_vector_type(2)));
-        v2h ph, pl;
-        ph[0] = h0[j]; ph[1] = h1[j];
-        pl[0] = l0[j]; pl[1] = l1[j];
-        *reinterpret_cast<v2h*>(&Vh[(c4 * 4 + j) * VP + 2 * kp]) = ph;
-        *reinterpret_cast<v2h*>(&Vl[(c4 * 4 + j) * VP + 2 * kp]) = pl;
-      }
-    }
+    if (!PL) attn_split_kv_tile<D, DV>(kb, p.k_sT, vb, p.v_sT, c.tix, k0, p.Nk, 0, Kh, Kl, KP, Vh, Vl, VP);
     if (!(PL && PF)) __syncthreads();
 
     // S^T = K . Q^T
@@ -474,13 +499,13 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const AttnArgs p) {
     // online softmax over the 32 keys of this tile (16 in my registers, 16 in lane^32's)
     float mt = -INFINITY;
     if (p.biasT || p.maskT) {
-      const float* bt = p.biasT ? p.biasT + (long)h * p.Nk * p.Nq : nullptr;
-      const float* mk = p.maskT ? p.maskT + (long)(b % p.nmask) * p.Nk * p.Nq : nullptr;
+      const float* bt = p.biasT ? p.biasT + (long)c.h * p.Nk * p.Nq : nullptr;
+      const float* mk = p.maskT ? p.maskT + (long)(c.b % p.nmask) * p.Nk * p.Nq : nullptr;
       float add[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const long o = (qok && key < p.Nk) ? (long)key * p.Nq + q : 0;
+        const long o = (qok && key < p.Nk) ? (long)key * p.Nq + c.q : 0;
         add[r] = (bt ? bt[o] : 0.f) + (mk ? mk[o] : 0.f);
       }
 #pragma unroll
@@ -547,38 +572,11 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const AttnArgs p) {
   }
 
   if (PL && PF && gridDim.z > 1) {
-    if (qok) {
-      const long pr = ((long)blockIdx.z * gridDim.y + blockIdx.y) * p.Nq + q;
-      if (lh == 0) *reinterpret_cast<float2*>(p.part_ml + pr * 2) = make_float2(m_run, l_run);
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(p.part_o + pr * DV + t * 32 + 8 * g + 4 * lh) =
-              make_float4(acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]);
-    }
+    if (qok) attn_store_partial<NT, DV>(acc, m_run, l_run, lh, p.part_o, p.part_ml, p.Nq, c.q);
     return;
   }
-  if (qok) {      // padded query rows (q >= Nq) store nothing and are never flagged
-    const float inv = 1.f / (l_run * (PSC * VSC));
-    const long oo = (long)sample * p.o_sB + (long)h * p.o_sH + (long)qrow * p.o_sT;
-    bool bad = false;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 o4 = make_float4(acc[t][4 * g] * inv, acc[t][4 * g + 1] * inv, acc[t][4 * g + 2] * inv,
-                                acc[t][4 * g + 3] * inv);
-        const int dd = t * 32 + 8 * g + 4 * lh;
-        if (p.res) {
-          const float4 rr = *reinterpret_cast<const float4*>(p.res + oo + dd);
-          o4.x += rr.x; o4.y += rr.y; o4.z += rr.z; o4.w += rr.w;
-        }
-        bad |= nonfinite4(o4);
-        *reinterpret_cast<float4*>(p.o + oo + dd) = o4;
-      }
-    report_nonfinite(p.status, bad);
-  }
+  if (qok)      // padded query rows (q >= Nq) store nothing and are never flagged
+    attn_store_row<NT>(acc, 1.f / (l_run * (PSC * VSC)), lh, p.res, p.o, c.head(p.o_sB, p.o_sH) + (long)c.qrow * p.o_sT, p.status);
 }
 
 // ------------------------------------------------------------------ the same kernel as a software pipeline over the key tiles
@@ -594,35 +592,19 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const AttnArgs p) {
 // arithmetic per query row is that of attn_f16x3_kernel (same products, same order), so results are bit-identical.
 template <int D, int DV>
 __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnArgs p) {
-  constexpr int KP = D + 8, VP = 36, NS = D / 16, NT = DV / 32;
-  constexpr float QSC = 64.f, KSC = ATT_KSC, PSC = ATT_PSC, VSC = ATT_VSC;
+  constexpr int KP = D + ATT_KPAD, VP = ATT_VP, NS = D / 16, NT = DV / 32;
+  constexpr float QSC = ATT_QSC, KSC = ATT_KSC, PSC = ATT_PSC, VSC = ATT_VSC;
   typedef AttnImg<D, DV> I;
   static_assert(I::KP == KP && I::VP == VP, "LDS layout = plane image layout");
   constexpr int KT = I::KTI, VT = I::VTI;                 // halves per staged K / V tile (hi + lo planes) = the plane images
   __shared__ __attribute__((aligned(16))) _Float16 smem[2 * KT + 2 * VT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
-  const int b = blockIdx.y / p.Hh, h = blockIdx.y % p.Hh;
-  const int q = blockIdx.x * 128 + wave * 32 + li;
-  const bool qok = q < p.Nq;
+  const AttnCoord c = attn_coord<false>(p);
+  const bool qok = c.qok;
 
   v8h qh[NS], ql[NS];
-  {
-    const float* qp = p.q + (long)b * p.q_sB + (long)h * p.q_sH + (long)(qok ? q : 0) * p.q_sT + 8 * lh;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      float4 a = *reinterpret_cast<const float4*>(qp + 16 * s);
-      float4 c = *reinterpret_cast<const float4*>(qp + 16 * s + 4);
-      if (!qok) { a = make_float4(0.f, 0.f, 0.f, 0.f); c = a; }
-      const float f[8] = {a.x * QSC, a.y * QSC, a.z * QSC, a.w * QSC, c.x * QSC, c.y * QSC, c.z * QSC, c.w * QSC};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        _Float16 hh, ll;
-        split_f16(f[e], hh, ll);
-        qh[s][e] = hh; ql[s][e] = ll;
-      }
-    }
-  }
+  attn_load_q<NS>(p.q + c.head(p.q_sB, p.q_sH) + (long)c.qrow * p.q_sT, qok, lh, qh, ql);
   v16f acc[NT], sc, scn;
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -797,38 +779,12 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnArgs p) {
   }
 
   if (gridDim.z > 1) {
-    if (qok) {
-      const long pr = ((long)blockIdx.z * gridDim.y + blockIdx.y) * p.Nq + q;
-      if (lh == 0) *reinterpret_cast<float2*>(p.part_ml + pr * 2) = make_float2(m_run, l_run);
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(p.part_o + pr * DV + t * 32 + 8 * g + 4 * lh) =
-              make_float4(acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]);
-    }
+    if (qok) attn_store_partial<NT, DV>(acc, m_run, l_run, lh, p.part_o, p.part_ml, p.Nq, c.q);
     return;
   }
-  if (qok) {      // padded query rows (q >= Nq) store nothing and are never flagged
-    const float inv = 1.f / (l_run * (PSC * VSC));
-    const long oo = (long)b * p.o_sB + (long)h * p.o_sH + (long)q * p.o_sT;
-    bool bad = false;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 o4 = make_float4(acc[t][4 * g] * inv, acc[t][4 * g + 1] * inv, acc[t][4 * g + 2] * inv,
-                                acc[t][4 * g + 3] * inv);
-        const int dd = t * 32 + 8 * g + 4 * lh;
-        if (p.res) {
-          const float4 rr = *reinterpret_cast<const float4*>(p.res + oo + dd);
-          o4.x += rr.x; o4.y += rr.y; o4.z += rr.z; o4.w += rr.w;
-        }
-        bad |= nonfinite4(o4);
-        *reinterpret_cast<float4*>(p.o + oo + dd) = o4;
-      }
-    report_nonfinite(p.status, bad);
-  }
+  if (qok)      // padded query rows (q >= Nq) store nothing and are never flagged
+    // row q itself, not qrow (equal here: no token index): keeping qrow alive to this point costs two vector registers
+    attn_store_row<NT>(acc, 1.f / (l_run * (PSC * VSC)), lh, p.res, p.o, c.head(p.o_sB, p.o_sH) + (long)c.q * p.o_sT, p.status);
 }
 
 // Key split, second pass: the slices' partial results are merged in fixed order z = 0, 1, .. (deterministic):
@@ -1045,6 +1001,40 @@ extern "C" int mspi_mvit_qk_augment(const MspiMvitAugDesc* d, const float* q, co
   return check_launch("mspi_mvit_qk_augment");
 }
 
+// ------------------------------------------------------------------ attention: host side
+// The instantiated (D, Dv) pairs are written down here and in one other place, their cases in attn_launch's switch (which
+// turns the run-time pair into template arguments).  attn_pair_ok and the refusal text read this table.
+struct AttnPair { int D, Dv; };
+static constexpr AttnPair kAttnPairs[] = {{32, 32}, {64, 64}, {96, 96}, {128, 128}, {128, 96}, {144, 96}, {160, 96}};
+
+static bool attn_pair_ok(int D, int Dv) {
+  for (const AttnPair& p : kAttnPairs)
+    if (p.D == D && p.Dv == Dv) return true;
+  return false;
+}
+
+static int attn_refuse_pair(const MspiAttnDesc* d) {
+  static const std::string pairs = [] {
+    std::string t;
+    for (const AttnPair& p : kAttnPairs) t += (t.empty() ? "(" : ",(") + std::to_string(p.D) + "," + std::to_string(p.Dv) + ")";
+    return t;
+  }();
+  set_error("mspi_attn_fwd: (D=%d, Dv=%d) not in {%s}", d->D, d->Dv, pairs.c_str());
+  return MSPI_EINVAL;
+}
+
+// The A/B switches, read once per process.  MSPI_ATTN_KSPLIT=0: no key split.  MSPI_ATTN_PF=0: the next tile's planes are
+// not fetched into registers under the current tile's MFMAs (same-box A/B on the MViTv2-S shapes 2.377 -> 2.244 ms per forward
+// with the prefetch, better or equal on every shape).  MSPI_ATTN_PIPE=0: no software-pipelined form (attn_pipe_kernel).
+struct AttnEnv { bool ksplit, pf, pipe; };
+static const AttnEnv& attn_env() {
+  static const AttnEnv env = [] {
+    auto on = [](const char* name) { const char* v = getenv(name); return !(v && v[0] == '0'); };
+    return AttnEnv{on("MSPI_ATTN_KSPLIT"), on("MSPI_ATTN_PF"), on("MSPI_ATTN_PIPE")};
+  }();
+  return env;
+}
+
 static long attn_nkp(const MspiAttnDesc* d) { return ((long)d->Nk + 31) / 32 * 32; }
 
 // Key split for few-query shapes (MViTv2's last stage: 8 heads x 392 queries = 256 workgroups of up to 49 key tiles each, one
@@ -1052,10 +1042,8 @@ static long attn_nkp(const MspiAttnDesc* d) { return ((long)d->Nk + 31) / 32 * 3
 // that the grid reaches two workgroups per CU and no slice is shorter than 12 tiles (measured, batch 8: Nk = 1568 195.8 ->
 // 173.0 us, but Nk = 392 in two slices of 7 tiles 66.7 -> 71.6 us: the merge pass costs more than the second workgroup per
 // CU gains -- a CU retires one 128 x 32 tile step per ~3.3 us however many workgroups share it); 1 = no split.
-// MSPI_ATTN_KSPLIT=0: off.
 static int attn_ksplit(const MspiAttnDesc* d) {
-  static const char* env = getenv("MSPI_ATTN_KSPLIT");
-  if (env && env[0] == '0') return 1;
+  if (!attn_env().ksplit) return 1;
   const long wgs = (((long)d->Nq + 127) / 128) * d->B * d->Hh;
   const int ntile = (int)(attn_nkp(d) / 32);
   int split = (int)(512 / (wgs > 0 ? wgs : 1));
@@ -1065,44 +1053,27 @@ static int attn_ksplit(const MspiAttnDesc* d) {
   return split < 2 ? 1 : split;
 }
 
-// plane bytes: the larger of the plain layout and the per-tile image layout (attn_pipe_kernel; AttnImg<D, DV>)
-static size_t attn_planes_bytes(const MspiAttnDesc* d) {
-  const size_t plain = (size_t)d->B * d->Hh * 2 * attn_nkp(d) * (size_t)(d->D + d->Dv) * sizeof(_Float16);
-  const size_t kti = 2 * 32 * (size_t)(d->D + 8), vti = (2 * (size_t)d->Dv * 36 * 2 + 1023) / 1024 * 512;
-  const size_t img = (size_t)d->B * d->Hh * (attn_nkp(d) / 32) * (kti + vti) * sizeof(_Float16);
-  const size_t b = plain > img ? plain : img;
-  return (b + 15) & ~(size_t)15;
+// The workspace of mspi_attn_fwd_ws, byte offsets.  The K planes start at 0 in either form, the V planes follow them: plain
+// form [hi, lo][Nkp][D] and [hi, lo][Dv][Nkp] per (sequence, head), image form one AttnImg tile per 32 keys.  The two forms
+// share the space (the larger one, padded to 16 B, counts); the key split's partial results follow.
+struct AttnWs { size_t v_plain, v_img, part_o, part_ml, total; };
+static AttnWs attn_ws_layout(const MspiAttnDesc* d, int split) {
+  const size_t bh = (size_t)d->B * d->Hh, nkp = (size_t)attn_nkp(d), half = sizeof(_Float16);
+  AttnWs w;
+  w.v_plain = bh * 2 * nkp * (size_t)d->D * half;
+  w.v_img = bh * (nkp / 32) * (size_t)attn_img_k(d->D) * half;
+  const size_t plain = w.v_plain + bh * 2 * nkp * (size_t)d->Dv * half;
+  const size_t img = w.v_img + bh * (nkp / 32) * (size_t)attn_img_v(d->Dv) * half;
+  const size_t rows = split > 1 ? (size_t)split * bh * d->Nq : 0;      // partial rows: [z][B * Hh][Nq]
+  w.part_o = ((plain > img ? plain : img) + 15) & ~(size_t)15;
+  w.part_ml = w.part_o + rows * (size_t)d->Dv * sizeof(float);
+  w.total = w.part_ml + rows * 2 * sizeof(float);
+  return w;
 }
 
 extern "C" size_t mspi_attn_ws_bytes(const MspiAttnDesc* d) {
   if (!d || d->prec != MSPI_PREC_F16X3 || d->B <= 0 || d->Hh <= 0 || d->Nk <= 0) return 0;
-  const int split = attn_ksplit(d);
-  const size_t part = split > 1 ? (size_t)split * d->B * d->Hh * d->Nq * (size_t)(d->Dv + 2) * sizeof(float) : 0;
-  return attn_planes_bytes(d) + part;
-}
-
-static int attn_fwd_impl(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
-                         const float* biasT, const float* maskT, const int32_t* tok_idx, float* o, void* ws,
-                         mspi_stream_t stream);
-
-extern "C" int mspi_attn_fwd(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
-                             const float* biasT, const float* maskT, const int32_t* tok_idx, float* o,
-                             mspi_stream_t stream) {
-  return attn_fwd_impl(d, q, k, v, res, biasT, maskT, tok_idx, o, nullptr, stream);
-}
-
-extern "C" int mspi_attn_fwd_ws(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
-                                const float* biasT, const float* maskT, const int32_t* tok_idx, float* o, void* workspace,
-                                mspi_stream_t stream) {
-  MSPI_REQUIRE(workspace && aligned16(workspace), "mspi_attn_fwd_ws: workspace must be a 16-B aligned device buffer");
-  return attn_fwd_impl(d, q, k, v, res, biasT, maskT, tok_idx, o, workspace, stream);
-}
-
-static bool attn_pair_ok(int D, int Dv) {
-  switch (D * 1000 + Dv) {
-    case 32032: case 64064: case 96096: case 128128: case 128096: case 144096: case 160096: return true;
-    default: return false;
-  }
+  return attn_ws_layout(d, attn_ksplit(d)).total;
 }
 
 // The kernels of this launch (include/mspi_hip.h, mspi_attn_variant): kind * 10^7 + D * 10^4 + Dv * 10 + merge, kind 1 = fp32,
@@ -1113,14 +1084,9 @@ static int attn_select(const MspiAttnDesc* d, bool bias, bool mask, bool tok, bo
   const int pair = d->D * 10000 + d->Dv * 10;
   if (d->prec == MSPI_PREC_F32) return 10000000 + pair;
   if (!ws) return 20000000 + pair;
-  // next tile's planes fetched into registers under the current tile's MFMAs: same-box A/B on the MViTv2-S shapes 2.377 ->
-  // 2.244 ms per forward, better or equal on every shape.  MSPI_ATTN_PF=0 switches it off for an A/B.
-  static const char* pf_env = getenv("MSPI_ATTN_PF");
-  const bool pf = !(pf_env && pf_env[0] == '0');
-  // software-pipelined form (attn_pipe_kernel) wherever there is no bias, mask or token index; MSPI_ATTN_PIPE=0: off
-  static const char* pipe_env = getenv("MSPI_ATTN_PIPE");
-  const bool plain = !bias && !mask && !tok;
-  const bool pipe = pf && plain && !(pipe_env && pipe_env[0] == '0');
+  const bool pf = attn_env().pf;
+  const bool plain = !bias && !mask && !tok;      // the pipeline and the key split have no bias, mask or token index
+  const bool pipe = pf && plain && attn_env().pipe;
   const int split = (pf && plain) ? attn_ksplit(d) : 1;
   return (pipe ? 50000000 : pf ? 30000000 : 40000000) + pair + (split > 1 ? 1 : 0);
 }
@@ -1128,6 +1094,59 @@ static int attn_select(const MspiAttnDesc* d, bool bias, bool mask, bool tok, bo
 extern "C" int mspi_attn_variant(const MspiAttnDesc* d, int32_t has_bias, int32_t has_mask, int32_t has_tok, int32_t has_ws) {
   MSPI_REQUIRE(d, "mspi_attn_variant: null descriptor");
   return attn_select(d, has_bias != 0, has_mask != 0, has_tok != 0, has_ws != 0);
+}
+
+static AttnArgs attn_args(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
+                          const float* biasT, const float* maskT, const int32_t* tok_idx, float* o) {
+  AttnArgs a;
+  a.q = q; a.k = k; a.v = v; a.res = res; a.biasT = biasT; a.maskT = maskT; a.tok_idx = tok_idx; a.o = o;
+  a.B = d->B; a.Hh = d->Hh; a.Nq = d->Nq; a.Nk = d->Nk; a.nmask = d->nmask > 0 ? d->nmask : 1;
+  a.nwin = d->nwin > 0 ? d->nwin : 1;
+  a.kp = a.vp = nullptr; a.Nkp = 0; a.part_o = a.part_ml = nullptr;
+  a.q_sB = d->q_sB; a.q_sH = d->q_sH; a.q_sT = d->q_sT;
+  a.k_sB = d->k_sB; a.k_sH = d->k_sH; a.k_sT = d->k_sT;
+  a.v_sB = d->v_sB; a.v_sH = d->v_sH; a.v_sT = d->v_sT;
+  a.o_sB = d->o_sB; a.o_sH = d->o_sH; a.o_sT = d->o_sT;
+  a.scale = d->scale;
+  a.status = g_status_word;
+  return a;
+}
+
+// Every launch of one pair: kind as in attn_select; the planes kernel runs before the kernels that read its planes, the merge
+// pass after a key split.
+struct AttnGrids { dim3 attn, planes, merge; };
+template <int D, int DV>
+static void attn_launch_pair(int kind, int split, const AttnGrids& g, const AttnArgs& a, hipStream_t s) {
+  const dim3 block(256);
+  switch (kind) {
+    case 1: hipLaunchKernelGGL((attn_kernel<D, DV>), g.attn, block, 0, s, a); return;
+    case 2: hipLaunchKernelGGL((attn_f16x3_kernel<D, DV>), g.attn, block, 0, s, a); return;
+    case 3:
+      hipLaunchKernelGGL((attn_kv_planes_kernel<D, DV>), g.planes, block, 0, s, a);
+      hipLaunchKernelGGL((attn_f16x3_kernel<D, DV, true, true>), g.attn, block, 0, s, a);
+      break;
+    case 4:
+      hipLaunchKernelGGL((attn_kv_planes_kernel<D, DV>), g.planes, block, 0, s, a);
+      hipLaunchKernelGGL((attn_f16x3_kernel<D, DV, true, false>), g.attn, block, 0, s, a);
+      break;
+    default:
+      hipLaunchKernelGGL((attn_kv_planes_kernel<D, DV, true>), g.planes, block, 0, s, a);
+      hipLaunchKernelGGL((attn_pipe_kernel<D, DV>), g.attn, block, 0, s, a);
+  }
+  if (split > 1) hipLaunchKernelGGL((attn_merge_kernel<DV>), g.merge, block, 0, s, a, split);
+}
+
+static bool attn_launch(int D, int Dv, int kind, int split, const AttnGrids& g, const AttnArgs& a, hipStream_t s) {
+  switch (D * 1000 + Dv) {      // one case per row of kAttnPairs
+    case 32032: attn_launch_pair<32, 32>(kind, split, g, a, s); return true;
+    case 64064: attn_launch_pair<64, 64>(kind, split, g, a, s); return true;
+    case 96096: attn_launch_pair<96, 96>(kind, split, g, a, s); return true;
+    case 128128: attn_launch_pair<128, 128>(kind, split, g, a, s); return true;
+    case 128096: attn_launch_pair<128, 96>(kind, split, g, a, s); return true;
+    case 144096: attn_launch_pair<144, 96>(kind, split, g, a, s); return true;
+    case 160096: attn_launch_pair<160, 96>(kind, split, g, a, s); return true;
+    default: return false;
+  }
 }
 
 static int attn_fwd_impl(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
@@ -1145,84 +1164,38 @@ static int attn_fwd_impl(const MspiAttnDesc* d, const float* q, const float* k, 
                "mspi_attn_fwd: a token index needs nwin > 0, B %% nwin == 0 and Nq == Nk");
   MSPI_REQUIRE(d->prec == MSPI_PREC_F32 || d->prec == MSPI_PREC_F16X3, "mspi_attn_fwd: prec = %d", d->prec);
   const int variant = attn_select(d, biasT != nullptr, maskT != nullptr, tok_idx != nullptr, ws != nullptr);
-  MSPI_REQUIRE(variant > 0, "mspi_attn_fwd: (D=%d, Dv=%d) not in {(32,32),(64,64),(96,96),(128,128),(128,96),(144,96),(160,96)}",
-               d->D, d->Dv);
+  if (variant <= 0) return attn_refuse_pair(d);
   const int kind = variant / 10000000;
-  AttnArgs a;
-  a.q = q; a.k = k; a.v = v; a.res = res; a.biasT = biasT; a.maskT = maskT; a.tok_idx = tok_idx; a.o = o;
-  a.B = d->B; a.Hh = d->Hh; a.Nq = d->Nq; a.Nk = d->Nk; a.nmask = d->nmask > 0 ? d->nmask : 1;
-  a.nwin = d->nwin > 0 ? d->nwin : 1;
-  a.kp = a.vp = nullptr; a.Nkp = 0; a.part_o = a.part_ml = nullptr;
-  a.q_sB = d->q_sB; a.q_sH = d->q_sH; a.q_sT = d->q_sT;
-  a.k_sB = d->k_sB; a.k_sH = d->k_sH; a.k_sT = d->k_sT;
-  a.v_sB = d->v_sB; a.v_sH = d->v_sH; a.v_sT = d->v_sT;
-  a.o_sB = d->o_sB; a.o_sH = d->o_sH; a.o_sT = d->o_sT;
-  a.scale = d->scale;
-  a.status = g_status_word;
-  dim3 grid((unsigned)((d->Nq + 127) / 128), (unsigned)(d->B * d->Hh));
-  hipStream_t s = (hipStream_t)stream;
-  const int key = d->D * 1000 + d->Dv;
-  if (kind >= 3) {      // K / V planes in the workspace
+  const int split = (variant % 10) ? attn_ksplit(d) : 1;
+  AttnArgs a = attn_args(d, q, k, v, res, biasT, maskT, tok_idx, o);
+  AttnGrids g;
+  g.attn = dim3((unsigned)((d->Nq + 127) / 128), (unsigned)(d->B * d->Hh), (unsigned)split);
+  if (kind >= 3) {      // K / V planes in the workspace: images for the pipeline, plain planes for the others
+    const AttnWs w = attn_ws_layout(d, split);
+    unsigned char* base = reinterpret_cast<unsigned char*>(ws);
     a.Nkp = (int)attn_nkp(d);
-    a.kp = reinterpret_cast<_Float16*>(ws);
-    a.vp = a.kp + (size_t)d->B * d->Hh * 2 * a.Nkp * d->D;
-    const size_t img_k = (size_t)d->B * d->Hh * (a.Nkp / 32) * 2 * 32 * (size_t)(d->D + 8);   // halves of all K images
-    dim3 pgrid((unsigned)(a.Nkp / 32), (unsigned)(d->B * d->Hh));
-    const int split = (variant % 10) ? attn_ksplit(d) : 1;
+    a.kp = reinterpret_cast<_Float16*>(base);
+    a.vp = reinterpret_cast<_Float16*>(base + (kind == 5 ? w.v_img : w.v_plain));
     if (split > 1) {
-      a.part_o = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(ws) + attn_planes_bytes(d));
-      a.part_ml = a.part_o + (size_t)split * d->B * d->Hh * d->Nq * d->Dv;
-      grid.z = (unsigned)split;
+      a.part_o = reinterpret_cast<float*>(base + w.part_o);
+      a.part_ml = reinterpret_cast<float*>(base + w.part_ml);
     }
-    const dim3 mgrid((unsigned)(((long)d->B * d->Hh * d->Nq * (d->Dv / 4) + 255) / 256));
-#define MSPI_ATTN_PL(DD, DVV)                                                                        \
-  case DD * 1000 + DVV:                                                                              \
-    if (kind == 5) {                                                                                 \
-      a.vp = a.kp + img_k;                                                                           \
-      hipLaunchKernelGGL((attn_kv_planes_kernel<DD, DVV, true>), pgrid, dim3(256), 0, s, a);         \
-      hipLaunchKernelGGL((attn_pipe_kernel<DD, DVV>), grid, dim3(256), 0, s, a);                     \
-    } else {                                                                                         \
-      hipLaunchKernelGGL((attn_kv_planes_kernel<DD, DVV>), pgrid, dim3(256), 0, s, a);               \
-      if (kind == 3) hipLaunchKernelGGL((attn_f16x3_kernel<DD, DVV, true, true>), grid, dim3(256), 0, s, a);  \
-      else hipLaunchKernelGGL((attn_f16x3_kernel<DD, DVV, true, false>), grid, dim3(256), 0, s, a);  \
-    }                                                                                                \
-    if (split > 1) hipLaunchKernelGGL((attn_merge_kernel<DVV>), mgrid, dim3(256), 0, s, a, split);   \
-    break;
-    switch (key) {
-      MSPI_ATTN_PL(32, 32) MSPI_ATTN_PL(64, 64) MSPI_ATTN_PL(96, 96) MSPI_ATTN_PL(128, 128) MSPI_ATTN_PL(128, 96) MSPI_ATTN_PL(144, 96) MSPI_ATTN_PL(160, 96)
-      default:
-        set_error("mspi_attn_fwd_ws: (D=%d, Dv=%d) not in {(32,32),(64,64),(96,96),(128,128),(128,96),(144,96),(160,96)}", d->D, d->Dv);
-        return MSPI_EINVAL;
-    }
-#undef MSPI_ATTN_PL
-    return check_launch("mspi_attn_fwd_ws");
+    g.planes = dim3((unsigned)(a.Nkp / 32), (unsigned)(d->B * d->Hh));
+    g.merge = dim3((unsigned)(((long)d->B * d->Hh * d->Nq * (d->Dv / 4) + 255) / 256));
   }
-  if (kind == 2) {
-    switch (key) {
-      case 32032: hipLaunchKernelGGL((attn_f16x3_kernel<32, 32>), grid, dim3(256), 0, s, a); break;
-      case 64064: hipLaunchKernelGGL((attn_f16x3_kernel<64, 64>), grid, dim3(256), 0, s, a); break;
-      case 96096: hipLaunchKernelGGL((attn_f16x3_kernel<96, 96>), grid, dim3(256), 0, s, a); break;
-      case 128128: hipLaunchKernelGGL((attn_f16x3_kernel<128, 128>), grid, dim3(256), 0, s, a); break;
-      case 128096: hipLaunchKernelGGL((attn_f16x3_kernel<128, 96>), grid, dim3(256), 0, s, a); break;
-      case 144096: hipLaunchKernelGGL((attn_f16x3_kernel<144, 96>), grid, dim3(256), 0, s, a); break;
-      case 160096: hipLaunchKernelGGL((attn_f16x3_kernel<160, 96>), grid, dim3(256), 0, s, a); break;
-      default:
-        set_error("mspi_attn_fwd: (D=%d, Dv=%d) not in {(32,32),(64,64),(96,96),(128,128),(128,96),(144,96),(160,96)}", d->D, d->Dv);
-        return MSPI_EINVAL;
-    }
-    return check_launch("mspi_attn_fwd");
-  }
-  switch (key) {
-    case 32032: hipLaunchKernelGGL((attn_kernel<32, 32>), grid, dim3(256), 0, s, a); break;
-    case 64064: hipLaunchKernelGGL((attn_kernel<64, 64>), grid, dim3(256), 0, s, a); break;
-    case 96096: hipLaunchKernelGGL((attn_kernel<96, 96>), grid, dim3(256), 0, s, a); break;
-    case 128128: hipLaunchKernelGGL((attn_kernel<128, 128>), grid, dim3(256), 0, s, a); break;
-    case 128096: hipLaunchKernelGGL((attn_kernel<128, 96>), grid, dim3(256), 0, s, a); break;
-    case 144096: hipLaunchKernelGGL((attn_kernel<144, 96>), grid, dim3(256), 0, s, a); break;
-    case 160096: hipLaunchKernelGGL((attn_kernel<160, 96>), grid, dim3(256), 0, s, a); break;
-    default:
-      set_error("mspi_attn_fwd: (D=%d, Dv=%d) not in {(32,32),(64,64),(96,96),(128,128),(128,96),(144,96),(160,96)}", d->D, d->Dv);
-      return MSPI_EINVAL;
-  }
-  return check_launch("mspi_attn_fwd");
+  if (!attn_launch(d->D, d->Dv, kind, split, g, a, (hipStream_t)stream)) return attn_refuse_pair(d);
+  return check_launch(kind >= 3 ? "mspi_attn_fwd_ws" : "mspi_attn_fwd");
+}
+
+extern "C" int mspi_attn_fwd(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
+                             const float* biasT, const float* maskT, const int32_t* tok_idx, float* o,
+                             mspi_stream_t stream) {
+  return attn_fwd_impl(d, q, k, v, res, biasT, maskT, tok_idx, o, nullptr, stream);
+}
+
+extern "C" int mspi_attn_fwd_ws(const MspiAttnDesc* d, const float* q, const float* k, const float* v, const float* res,
+                                const float* biasT, const float* maskT, const int32_t* tok_idx, float* o, void* workspace,
+                                mspi_stream_t stream) {
+  MSPI_REQUIRE(workspace && aligned16(workspace), "mspi_attn_fwd_ws: workspace must be a 16-B aligned device buffer");
+  return attn_fwd_impl(d, q, k, v, res, biasT, maskT, tok_idx, o, workspace, stream);
 }

@@ -209,6 +209,69 @@ def test_production_shapes_keep_their_kernels():
     assert _attn_code((8, 4, 874, 874, 128, 128, F16X3, False, False, False, True, False)) == 51281281
 
 
+def _attn_ksplit(B, Hh, Nq, Nk):
+    """attn_ksplit of csrc/attn.hip restated: key slices so that the grid reaches 512 workgroups, none under 12 tiles, <= 8."""
+    wgs = (Nq + 127) // 128 * B * Hh
+    ntile = (Nk + 31) // 32
+    split = min(512 // max(wgs, 1), ntile // 12, 8)
+    while split > 1 and (split - 1) * ((ntile + split - 1) // split) >= ntile:      # every slice non-empty
+        split -= 1
+    return split if split > 1 else 1
+
+
+def _attn_ws_bytes(B, Hh, Nq, Nk, D, Dv):
+    """The workspace of mspi_attn_fwd_ws restated: f16 hi / lo planes of K and V (the larger of the plain layout and the
+    per-tile LDS images, padded to 16 B), then the key split's partial O and (max, sum)."""
+    nkp = (Nk + 31) // 32 * 32
+    plain = B * Hh * 2 * nkp * (D + Dv) * 2
+    kti, vti = 64 * (D + 8), (144 * Dv + 1023) // 1024 * 512
+    img = B * Hh * (nkp // 32) * (kti + vti) * 2
+    planes = (max(plain, img) + 15) // 16 * 16
+    split = _attn_ksplit(B, Hh, Nq, Nk)
+    return planes + (split * B * Hh * Nq * (Dv + 2) * 4 if split > 1 else 0)
+
+
+def test_attn_workspace_size_matches_its_layout():
+    """mspi_attn_ws_bytes against the layout restated above (MSPI_ATTN_KSPLIT unset): every workspace row of the ledger, the
+    sync block's shape, MViT's key-split and many-query stages, and pairs without kernels (the size query does not check
+    the pair).  fp32 needs no workspace."""
+    from mspi_amd import _lib
+    _no_switches()
+    lib = _lib.load()
+    shapes = [row[:6] for row in ATTN_LEDGER.values() if row[10]]
+    shapes += [(8, 4, 874, 874, 128, 128), (8, 8, 392, 1568, 160, 96), (8, 1, 25088, 392, 128, 96)]
+    shapes += [(2, 3, 50, 2000, 48, 80), (1, 2, 130, 33, 256, 16)]
+    assert len(shapes) == 3 * len(_PAIRS) + 5
+    splits = set()
+    for B, Hh, Nq, Nk, D, Dv in shapes:
+        assert lib.mspi_attn_ws_bytes(C.byref(_attn_desc(B, Hh, Nq, Nk, D, Dv, F16X3))) == _attn_ws_bytes(B, Hh, Nq, Nk, D, Dv), \
+            (B, Hh, Nq, Nk, D, Dv)
+        assert lib.mspi_attn_ws_bytes(C.byref(_attn_desc(B, Hh, Nq, Nk, D, Dv, F32))) == 0
+        splits.add(_attn_ksplit(B, Hh, Nq, Nk))
+    assert {1, 2}.issubset(splits) and max(splits) > 2      # the cases hold unsplit, two-slice and wider key splits
+
+
+def test_attn_refusal_names_every_instantiated_pair():
+    """A (D, Dv) without kernels is refused by both launches with the full list of pairs, in order; the variant query says -1.
+    Nothing launches: the pair is checked on the host."""
+    import ctypes
+    from mspi_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_float * 72)()
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)
+    listed = ",".join("(%d,%d)" % pair for pair in _PAIRS)
+    for D, Dv in ((48, 48), (96, 128), (128, 64), (160, 160)):
+        for prec in (F32, F16X3):
+            d = _attn_desc(1, 1, 1, 1, D, Dv, prec)
+            want = ("mspi_attn_fwd: (D=%d, Dv=%d) not in {%s}" % (D, Dv, listed)).encode()
+            assert lib.mspi_attn_fwd(C.byref(d), p, p, p, None, None, None, None, p, None) == -1
+            assert lib.mspi_last_error() == want
+            assert lib.mspi_attn_fwd_ws(C.byref(d), p, p, p, None, None, None, None, p, p, None) == -1
+            assert lib.mspi_last_error() == want
+            for flags in range(16):
+                assert lib.mspi_attn_variant(C.byref(d), flags & 1, (flags >> 1) & 1, (flags >> 2) & 1, flags >> 3) == -1
+
+
 # ------------------------------------------------------------------------------------------------------------ GPU tests
 def _rel_close(got, ref, tol, what):
     """max |got - ref| <= tol * max |ref| (no floor: down-scaled outputs keep their relative bar)."""
@@ -352,6 +415,27 @@ def test_attn_ledger_kernel_vs_fp64(dev, code):
     assert variant == code
     _rel_close(out, ref, 1e-5, "attention variant %d" % code)
     assert not E.range_flag(), "in-range attention flagged as non-finite"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D,Dv", _PAIRS)
+def test_attn_forms_bit_identical(dev, D, Dv):
+    """The f16x3 forms of one (D, Dv) give the same bits: K / V split by every query tile (kind 2) against the software
+    pipeline on plane images (kind 5), and, with token index + bias + mask, against prefetched plain planes (kind 3).
+    97 keys = three full tiles plus one key, 71 = two tiles plus 7 (both lane halves of the key tail), ragged query tiles,
+    several sequences and heads; residual for the MViT widths."""
+    from mspi_amd import engine as E
+    _no_switches()
+    pair = D * 10000 + Dv * 10
+    res = D != Dv
+    for shape, form, with_ws in (((2, 2, 97, 97), False, 50000000), ((4, 2, 71, 71), True, 30000000)):
+        row = shape + (D, Dv, F16X3, form, form, form, False, res)
+        t, _ = _attn_inputs(row, pair + form)
+        direct, code = _attn_direct(E, row, t, dev)
+        assert code == 20000000 + pair
+        planes, code = _attn_direct(E, row[:10] + (True, res), t, dev)
+        assert code == with_ws + pair
+        assert not torch.isnan(direct).any() and torch.equal(direct, planes)
 
 
 def _mvit_case(q_thw, k_thw, heads, B, seed, hd=96):
