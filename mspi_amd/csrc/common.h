@@ -158,5 +158,7 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// torch.min: a NaN in either argument is the result (fminf would drop it, and a constant map would score SIM = 1)
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? a + b : fminf(a, b); }
 
 }  // namespace mspi

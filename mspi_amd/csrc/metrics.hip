@@ -76,7 +76,7 @@ __global__ __launch_bounds__(MT) void saliency_metrics_kernel(const float* __res
     kl += gp * logf(eps + gp / (sp + eps));
     const float sz = (s - mean_s) / std_s, gz = (g - mean_g) / std_g;
     ab = fmaf(sz, gz, ab); aa = fmaf(sz, sz, aa); bb = fmaf(gz, gz, bb);
-    sim += fminf((s - mns) * rs / ns, (g - mng) * rg / ng);
+    sim += min_nan((s - mns) * rs / ns, (g - mng) * rg / ng);
     if (f_) ns_f += (s - mean_s) / (std_s + eps) * f_[i];
   }
   kl = block_sum(kl, sh); ab = block_sum(ab, sh); aa = block_sum(aa, sh); bb = block_sum(bb, sh);

@@ -57,7 +57,10 @@ __global__ __launch_bounds__(256) void logspec_kernel(const float* __restrict__ 
     const float p = (float)(re * re + im * im);
     lp[q] = logf(p + 1e-6f);
   }
-  // mean / unbiased std over the 257 bins of this column
+  // mean / unbiased std over the 257 bins of this column.  This summation order is load-bearing: on digital silence all 257
+  // values are logf(1e-6f), and wave_sum's butterfly, the four partial sums in this order and / 257 give that value back
+  // exactly, so the column is exactly 0 (tests/test_logspec_kernel.py pins it).  That holds for this value and its 1-ulp
+  // neighbours, not for every float: whoever reorders the sum should centre the values on lp[0] of thread 0 first.
   float s = lp[0] + (tid == 0 ? lp[1] : 0.f);
   s = wave_sum(s);
   if ((tid & 63) == 0) red[tid >> 6] = s;

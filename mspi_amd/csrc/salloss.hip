@@ -174,7 +174,7 @@ __device__ __forceinline__ void sl_pass2(const float* __restrict__ x_, const flo
       const float sp = sv * invP, gp = g[k] * invG;
       const float r = gp / (sp + SL_EPS);
       a[0] += gp * logf(SL_EPS + r);
-      a[1] += fminf((sv - st.mns) * ks, (g[k] - st.mng) * kg);
+      a[1] += min_nan((sv - st.mns) * ks, (g[k] - st.mng) * kg);
       a[2] -= r * (r / (SL_EPS + r)) * sp;     // a_i = -gp^2 / ((sp + eps)(eps (sp + eps) + gp)) = -r^2 / (eps + r)
     }
   }
