@@ -54,7 +54,17 @@ const char* mspi_last_error(void);
  * results and store 1 into *word when one is inf or NaN -- whatever the cause (operand out of range, non-finite input).
  * `word` must be device-visible: a 4-byte word of pinned host memory (hipHostMalloc / torch pin_memory) lets the caller read
  * it without a device call, after the event that covers the launches; the caller clears it.  NULL (default): no report.
- * Process-global; set it before launching from several threads. */
+ * Process-global; set it before launching from several threads.
+ *
+ * Non-finite data (tests/test_nonfinite_ledger.py holds every entry point to it): a NaN or Inf in a floating-point operand
+ * never leaves an entry point as plausible finite data without a trace.  Every output that depends on it is non-finite
+ * (PROPAGATE), or *word is 1 (FLAG); outputs that do not depend on it are unaffected.
+ *   FLAG       the GEMM family on its pre-activation results (the seven above, mspi_conv_halo_fwd, mspi_x3d_ca_fwd: their
+ *              ReLU is fmaxf, which turns a NaN into 0 after the check), attention on its stored outputs, and
+ *              mspi_postprocess_u8, whose u8 output cannot carry a NaN, on the resized map.
+ *   PROPAGATE  every other entry point with floating-point output, as torch does: ReLU and max keep a NaN
+ *              (mspi_x3d_stem_fwd, mspi_dwconv_fwd, mspi_maxpool_fwd, mspi_se_gate, mspi_layernorm_fwd / _sp_fwd,
+ *              mspi_upsample_fwd / _sum_fwd, mspi_bn_stats / _apply, the other row operations and training kernels). */
 int mspi_set_status_word(int32_t* device_visible_word);
 
 /* number of visible HIP devices whose arch is gfx950 (0 if none). */

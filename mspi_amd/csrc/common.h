@@ -160,5 +160,11 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 // torch.min: a NaN in either argument is the result (fminf would drop it, and a constant map would score SIM = 1)
 __device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? a + b : fminf(a, b); }
+// torch.max / torch.relu likewise: fmaxf(NaN, 0) is a clean 0, so a poisoned activation would leave a kernel that ends in
+// fmaxf as plausible data.  For the kernels OUTSIDE the GEMM family, whose epilogues flag the pre-activation instead
+// (report_nonfinite) and keep the one-instruction fmaxf of act_apply.  Same values as fmaxf on every non-NaN input (+-0 aside).
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float act_apply_nan(float v, int act) { return act == MSPI_ACT_RELU ? relu_nan(v) : act_apply(v, act); }
 
 }  // namespace mspi

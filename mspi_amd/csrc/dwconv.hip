@@ -86,10 +86,10 @@ __global__ __launch_bounds__(256) void dw_kernel(const DwArgs p) {
           if ((unsigned)w >= (unsigned)p.W) continue;
           const float4 xv = *reinterpret_cast<const float4*>(xr + (long)w * p.ldx);
           if (IS_MAX) {
-            acc.x = fmaxf(acc.x, xv.x);
-            acc.y = fmaxf(acc.y, xv.y);
-            acc.z = fmaxf(acc.z, xv.z);
-            acc.w = fmaxf(acc.w, xv.w);
+            acc.x = max_nan(acc.x, xv.x);
+            acc.y = max_nan(acc.y, xv.y);
+            acc.z = max_nan(acc.z, xv.z);
+            acc.w = max_nan(acc.w, xv.w);
           } else {
             const float4 wv = *reinterpret_cast<const float4*>(wr + (long)dw * p.C);
             acc.x = fmaf(xv.x, wv.x, acc.x);
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void dw_kernel(const DwArgs p) {
     if (!IS_MAX) {
       auto fin = [&](auto act_c) {
         constexpr int ACT = decltype(act_c)::value;
-        acc.x = act_apply(acc.x, ACT); acc.y = act_apply(acc.y, ACT); acc.z = act_apply(acc.z, ACT); acc.w = act_apply(acc.w, ACT);
+        acc.x = act_apply_nan(acc.x, ACT); acc.y = act_apply_nan(acc.y, ACT); acc.z = act_apply_nan(acc.z, ACT); acc.w = act_apply_nan(acc.w, ACT);
       };
       MSPI_DISPATCH_ACT(p.act, fin)
     }
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void dw_strip_kernel(const DwArgs p) {
         if (wo0 + o < p.Wo) {
           float4 v = acc[o];
           if (POOL) { psum.x += v.x; psum.y += v.y; psum.z += v.z; psum.w += v.w; }
-          v.x = act_apply(v.x, ACT); v.y = act_apply(v.y, ACT); v.z = act_apply(v.z, ACT); v.w = act_apply(v.w, ACT);
+          v.x = act_apply_nan(v.x, ACT); v.y = act_apply_nan(v.y, ACT); v.z = act_apply_nan(v.z, ACT); v.w = act_apply_nan(v.w, ACT);
           *reinterpret_cast<float4*>(p.y + (orow + o) * p.ldy + cv * 4) = v;
         }
       }
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(256) void dw_tile_kernel(const DwArgs p, int CG, in
           if (wo0 + o < p.Wo) {
             float4 v = acc[sh][o];
             if (POOL) { psum.x += v.x; psum.y += v.y; psum.z += v.z; psum.w += v.w; }
-            v.x = act_apply(v.x, ACT); v.y = act_apply(v.y, ACT); v.z = act_apply(v.z, ACT); v.w = act_apply(v.w, ACT);
+            v.x = act_apply_nan(v.x, ACT); v.y = act_apply_nan(v.y, ACT); v.z = act_apply_nan(v.z, ACT); v.w = act_apply_nan(v.w, ACT);
             *reinterpret_cast<float4*>(p.y + (orow + o) * p.ldy + cv * 4) = v;
           }
         }
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(256) void dw_lds_kernel(const DwArgs p, int CG, int
           if (wo + o < p.Wo) {
             float4 v = acc[o];
             if (POOL) { psum.x += v.x; psum.y += v.y; psum.z += v.z; psum.w += v.w; }
-            v.x = act_apply(v.x, ACT); v.y = act_apply(v.y, ACT); v.z = act_apply(v.z, ACT); v.w = act_apply(v.w, ACT);
+            v.x = act_apply_nan(v.x, ACT); v.y = act_apply_nan(v.y, ACT); v.z = act_apply_nan(v.z, ACT); v.w = act_apply_nan(v.w, ACT);
             *reinterpret_cast<float4*>(p.y + (orow + o) * p.ldy + cv * 4) = v;
           }
         }

@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void blur_exp_kernel(const float* __restrict__
 // bilinear resize (cv2.INTER_LINEAR: src = (dst + 0.5) * in/out - 0.5, clamped) + this workgroup's min/max ->
 // part[n][blockIdx.x][2]
 __global__ __launch_bounds__(256) void resize_minmax_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W,
-                                                            int Ho, int Wo, float* __restrict__ part) {
+                                                            int Ho, int Wo, float* __restrict__ part, int* status) {
   __shared__ float smin[4], smax[4];
   const int n = blockIdx.y;
   const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -59,6 +59,8 @@ __global__ __launch_bounds__(256) void resize_minmax_kernel(const float* __restr
         lh * ((1.f - lw) * xb[h1 * W + w0] + lw * xb[h1 * W + w1]);
     y[(long)n * Ho * Wo + idx] = v;
   }
+  // the u8 sink cannot carry a NaN (fminf / fmaxf below drop it, the quantiser writes 0): the status word is the only trace
+  report_nonfinite(status, nonfinite(v));
   float lo = ok ? v : INFINITY, hi = ok ? v : -INFINITY;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -165,7 +167,7 @@ extern "C" int mspi_postprocess_u8(const float* logmap, unsigned char* out, void
   float* part = resized + pp_r4((size_t)N * Ho * Wo);
   float* mm = part + pp_r4((size_t)N * 2 * nb);
   hipLaunchKernelGGL(blur_exp_kernel, dim3((H * W + 255) / 256, N), dim3(256), 0, s, logmap, blurred, H, W);
-  hipLaunchKernelGGL(resize_minmax_kernel, dim3(nb, N), dim3(256), 0, s, blurred, resized, H, W, Ho, Wo, part);
+  hipLaunchKernelGGL(resize_minmax_kernel, dim3(nb, N), dim3(256), 0, s, blurred, resized, H, W, Ho, Wo, part, g_status_word);
   hipLaunchKernelGGL(minmax_reduce_kernel, dim3(N), dim3(256), 0, s, part, nb, mm);
   hipLaunchKernelGGL(quantize_kernel, dim3((Ho * Wo + 4095) / 4096, N), dim3(256), 0, s, resized, mm, out, Ho * Wo);
   return check_launch("mspi_postprocess_u8");

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(BN_T) void bn_stats_kernel(const float* __restrict_
     const float m2 = b - a * a / n;
     float* rec = ws + (long)blockIdx.x * 2 * C;
     rec[c] = x[p0 * ld + c] + a / n;
-    rec[C + c] = m2 > 0.f ? m2 : 0.f;
+    rec[C + c] = relu_nan(m2);      // clamps rounding below 0; the NaN of a channel holding a NaN / Inf must stay one (common.h)
   }
 }
 
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   o.x = fmaf((v.x - mu.x) * rs.x, ga.x, be.x); o.y = fmaf((v.y - mu.y) * rs.y, ga.y, be.y);
   o.z = fmaf((v.z - mu.z) * rs.z, ga.z, be.z); o.w = fmaf((v.w - mu.w) * rs.w, ga.w, be.w);
   if (RELU) {
-    o.x = o.x > 0.f ? o.x : 0.f; o.y = o.y > 0.f ? o.y : 0.f; o.z = o.z > 0.f ? o.z : 0.f; o.w = o.w > 0.f ? o.w : 0.f;
+    o.x = relu_nan(o.x); o.y = relu_nan(o.y); o.z = relu_nan(o.z); o.w = relu_nan(o.w);      // NaN statistics stay visible (common.h)
   }
   *reinterpret_cast<float4*>(y + row * ldy + cv * 4) = o;
 }

@@ -63,10 +63,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       const float4 g = *reinterpret_cast<const float4*>(gamma + i * 4);
       const float4 b = *reinterpret_cast<const float4*>(beta + i * 4);
       float4 o;
-      o.x = act_apply((v[j].x - mean) * rstd * g.x + b.x, ACT);
-      o.y = act_apply((v[j].y - mean) * rstd * g.y + b.y, ACT);
-      o.z = act_apply((v[j].z - mean) * rstd * g.z + b.z, ACT);
-      o.w = act_apply((v[j].w - mean) * rstd * g.w + b.w, ACT);
+      o.x = act_apply_nan((v[j].x - mean) * rstd * g.x + b.x, ACT);
+      o.y = act_apply_nan((v[j].y - mean) * rstd * g.y + b.y, ACT);
+      o.z = act_apply_nan((v[j].z - mean) * rstd * g.z + b.z, ACT);
+      o.w = act_apply_nan((v[j].w - mean) * rstd * g.w + b.w, ACT);
       if (tr) {
         const float4 t = *reinterpret_cast<const float4*>(tr + i * 4);
         o.x += t.x; o.y += t.y; o.z += t.z; o.w += t.w;
@@ -168,14 +168,14 @@ __global__ __launch_bounds__(1024) void se_gate_kernel(const float* __restrict__
         s = fmaf(w1r[fi][j], c < C ? mean[c] : 0.f, s);
       }
       s = wave_sum(s);
-      if (lane == 0 && f < F) hid[f] = fmaxf(s + b1[f], 0.f);
+      if (lane == 0 && f < F) hid[f] = relu_nan(s + b1[f]);      // a NaN pool row stays a NaN gate (common.h)
     }
   } else {
     for (int f = wave; f < F; f += 16) {
       float s = 0.f;
       for (int c = lane; c < C; c += 64) s = fmaf(w1[(long)f * C + c], mean[c], s);
       s = wave_sum(s);
-      if (lane == 0) hid[f] = fmaxf(s + b1[f], 0.f);
+      if (lane == 0) hid[f] = relu_nan(s + b1[f]);
     }
   }
   __syncthreads();
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
     if (act != MSPI_ACT_NONE) {
       auto fin = [&](auto act_c) {
         constexpr int ACT = decltype(act_c)::value;
-        o.x = act_apply(o.x, ACT); o.y = act_apply(o.y, ACT); o.z = act_apply(o.z, ACT); o.w = act_apply(o.w, ACT);
+        o.x = act_apply_nan(o.x, ACT); o.y = act_apply_nan(o.y, ACT); o.z = act_apply_nan(o.z, ACT); o.w = act_apply_nan(o.w, ACT);
       };
       MSPI_DISPATCH_ACT(act, fin)
     }
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256) void upsample_sum_kernel(UpSumArgs a, float* _
     if (act != MSPI_ACT_NONE) {
       auto fin = [&](auto act_c) {
         constexpr int ACT = decltype(act_c)::value;
-        o.x = act_apply(o.x, ACT); o.y = act_apply(o.y, ACT); o.z = act_apply(o.z, ACT); o.w = act_apply(o.w, ACT);
+        o.x = act_apply_nan(o.x, ACT); o.y = act_apply_nan(o.y, ACT); o.z = act_apply_nan(o.z, ACT); o.w = act_apply_nan(o.w, ACT);
       };
       MSPI_DISPATCH_ACT(act, fin)
     }

@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void x3d_stem_kernel(const X3dStemArgs p) {
           float a = p.wt[c][z + 5];
 #pragma unroll
           for (int k = 0; k < 5; ++k) a = fmaf(ring[k][c], p.wt[c][z + k], a);
-          o[e] = fmaxf(a, 0.f);
+          o[e] = relu_nan(a);      // nothing runs before this kernel: a NaN pixel has to leave it as a NaN (common.h)
         }
         if (live) *reinterpret_cast<float4*>(yp + c4) = make_float4(o[0], o[1], o[2], o[3]);
       }

@@ -171,6 +171,11 @@ def _need_gpu(t):
 #  * RANGE CHECK on first sight of a pack (the first, autotuning forward -- the same "first input is representative"
 #    contract as cudnn.benchmark upstream, inference.py:19): max|x| of the layer's input outside [2^-5, 2^15] moves THAT layer
 #    to the fp32 MFMA path (exact fp32 fmaf chain, 5.3x the MFMA time) for good.  MSPI_RANGE_CHECK=0 disables it.
+# NON-FINITE DATA (include/mspi_hip.h at mspi_set_status_word; tests/test_nonfinite_ledger.py): a NaN or
+# Inf in an operand never leaves a kernel as plausible finite data without a trace.  The GEMM family (pre-activation
+# results), attention (stored outputs) and postprocess_u8 (whose u8 output cannot carry a NaN) FLAG it in the status word;
+# every other kernel with floating-point output PROPAGATES it as torch does (its ReLU and max keep a NaN), so the next GEMM
+# flags it or the map itself is NaN.  Outputs that do not depend on the poison are unaffected either way.
 _STATUS = {"word": None}
 RANGE_CHECK = {"on": _os.environ.get("MSPI_RANGE_CHECK", "1") != "0", "lo": 2.0 ** -5, "hi": 2.0 ** 15, "moved": []}
 
@@ -182,8 +187,9 @@ def _register_status_word():
 
 
 def range_flag(reset=True):
-    """True when a GEMM or attention kernel has produced a non-finite result since the last reset.  Host read of a pinned word: valid for
-    launches the caller has synchronised with (an event / stream / device sync)."""
+    """True when a flagging kernel (GEMM family, attention, postprocess_u8) has produced a non-finite result since the last
+    reset; the other kernels hand a NaN / Inf on in their output instead.  Host read of a pinned word: valid for launches the
+    caller has synchronised with (an event / stream / device sync)."""
     w = _STATUS["word"]
     if w is None:
         return False
@@ -194,7 +200,9 @@ def range_flag(reset=True):
 
 
 def check_range(sync=True):
-    """Raise MspiError when an f16x3 GEMM or attention has overflowed (or was fed non-finite data) since the last check."""
+    """Raise MspiError when an f16x3 GEMM or attention has overflowed, or a GEMM, attention or postprocess_u8 was fed
+    non-finite data, since the last check.  Kernels in front of them propagate a NaN / Inf rather than flag it, so a poisoned
+    forward raises here at its next GEMM, or returns a map that is itself non-finite."""
     if sync and torch.cuda.is_available():
         torch.cuda.synchronize()
     if range_flag():

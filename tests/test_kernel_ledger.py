@@ -350,7 +350,17 @@ def _attn_inputs(row, seed):
     nmask = 2
     mT = torch.where(torch.rand(nmask, Nk, Nq, generator=g) < 0.3, torch.tensor(-100.0), torch.tensor(0.0)) if mask else None
     ti = torch.randperm(Rq, generator=g).view(nwin, Nq).to(torch.int32) if tok else None
-    scale = D ** -0.5
+    t = dict(q=q, k=k, v=v, res=r, biasT=bT, maskT=mT, tok=ti, nwin=nwin, nmask=nmask, scale=D ** -0.5)
+    return t, _attn_ref(row, t)
+
+
+def _attn_ref(row, t):
+    """Explicit float64 softmax attention of the operands `t` of a ledger row (test_nonfinite_ledger.py evaluates it on
+    poisoned operands too)."""
+    B, Hh, Nq, Nk, D, Dv, prec, bias, mask, tok, ws, res = row
+    q, k, v, r, bT, mT, ti = (t[n] for n in ("q", "k", "v", "res", "biasT", "maskT", "tok"))
+    nwin, nmask, scale = t["nwin"], t["nmask"], t["scale"]
+    S, Rq = q.shape[0], q.shape[2]
     ref = torch.zeros(S, Hh, Rq, Dv, dtype=torch.float64)
     for bb in range(B):
         smp, win = bb // nwin, bb % nwin
@@ -365,17 +375,18 @@ def _attn_inputs(row, seed):
         if res:
             o = o + r[smp][:, rows].double()
         ref[smp][:, rows] = o
-    return dict(q=q, k=k, v=v, res=r, biasT=bT, maskT=mT, tok=ti, nwin=nwin, nmask=nmask, scale=scale), ref
+    return ref
 
 
-def _attn_direct(E, row, t, dev):
-    """mspi_attn_fwd / mspi_attn_fwd_ws straight from a ledger row.  Returns (output [S,Hh,Rq,Dv] on the GPU, variant)."""
+def _attn_direct(E, row, t, dev, fill=float("nan")):
+    """mspi_attn_fwd / mspi_attn_fwd_ws straight from a ledger row into an output prefilled with `fill`.  Returns (output
+    [S,Hh,Rq,Dv] on the GPU, variant)."""
     B, Hh, Nq, Nk, D, Dv, prec, bias, mask, tok, ws, res = row
     lib = E._lib.load()
     gq, gk, gv = (t[n].to(dev).contiguous() for n in ("q", "k", "v"))
     S, _, Rq, _ = gq.shape
     Rk = gk.shape[2]
-    o = torch.full((S, Hh, Rq, Dv), float("nan"), device=dev)
+    o = torch.full((S, Hh, Rq, Dv), fill, device=dev)
     d = _attn_desc(B, Hh, Nq, Nk, D, Dv, prec)
     d.nmask = t["nmask"] if mask else 0
     d.nwin = t["nwin"] if tok else 0
