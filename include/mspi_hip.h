@@ -16,7 +16,13 @@
  *   - every function returns 0 or a negative MSPI_E* code and never throws; the message
  *     is available from mspi_last_error() (thread-local)
  *   - kernels are stateless and re-entrant; launches go to `stream` and return
- *     immediately (graph-capture safe: no sync, no allocation, no memcpy inside)
+ *     immediately (graph-capture safe: no sync, no allocation, no memcpy inside).
+ *     That includes the FIRST call of a process, on any device and any thread: no entry
+ *     point initialises anything lazily, and none keeps a mutable static.  Host arrays
+ *     and descriptors are read during the call; a captured graph holds its own copy.
+ *     tests/test_launch_ledger.py holds every entry point to this (a source scan, one
+ *     capture + replay case per launching entry point, a cold-capture child process, a
+ *     second device); tests/test_replay_ledger.py replays every model through hipGraphs.
  */
 #ifndef MSPI_HIP_H
 #define MSPI_HIP_H
@@ -443,7 +449,10 @@ int mspi_neg_cosine(const float* p, const float* z, float* out, int32_t N, int32
 /* Saliency-map post-processing (inference.py:66-69,85-89; OpenCV upstream -- parity unpinned):
  * out[n] = uint8( round( 255 * minmax( resize_bilinear( exp( GaussianBlur11x11(logmap[n]) ), Ho x Wo ) ) ) ).
  * workspace: mspi_postprocess_workspace(...) bytes of device memory.  H, W >= 6: the blur reflects once, and for a map smaller
- * than its radius no reference defines the result (refused). */
+ * than its radius no reference defines the result (refused).
+ * Holds no state: the 11 Gaussian taps are computed on the host in every call and travel to the blur kernel by value in its
+ * arguments (a captured graph holds its own copy), so the first call of a process may be a captured one, and any device and
+ * any thread may call (tests/test_launch_ledger.py: the cold-capture child and the second-device test). */
 size_t mspi_postprocess_workspace(int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo);
 int mspi_postprocess_u8(const float* logmap, unsigned char* out, void* workspace, int32_t N, int32_t H, int32_t W,
                         int32_t Ho, int32_t Wo, mspi_stream_t stream);

@@ -9,9 +9,14 @@
 
 namespace mspi {
 
-__constant__ float c_gauss11[11];
+// the 11 taps travel by value in the kernel arguments (as X3dStemArgs carries the stem's weights): no device symbol, no
+// upload, nothing per process or per device to initialise; a captured graph holds its own copy
+struct Gauss11 {
+  float k[11];
+};
 
-__global__ __launch_bounds__(256) void blur_exp_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W) {
+__global__ __launch_bounds__(256) void blur_exp_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W,
+                                                       const Gauss11 g) {
   const int n = blockIdx.y;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= H * W) return;
@@ -27,9 +32,9 @@ __global__ __launch_bounds__(256) void blur_exp_kernel(const float* __restrict__
       int ww = w + j;
       ww = ww < 0 ? -ww : (ww >= W ? 2 * W - 2 - ww : ww);
       ww = ww < 0 ? 0 : (ww >= W ? W - 1 : ww);
-      row = fmaf(c_gauss11[j + 5], xb[hh * W + ww], row);
+      row = fmaf(g.k[j + 5], xb[hh * W + ww], row);
     }
-    acc = fmaf(c_gauss11[i + 5], row, acc);
+    acc = fmaf(g.k[i + 5], row, acc);
   }
   y[(long)n * H * W + idx] = expf(acc);
 }
@@ -147,18 +152,12 @@ extern "C" int mspi_postprocess_u8(const float* logmap, unsigned char* out, void
   // kernel does not and the oracle's reflect padding refuses -- there is nothing to pin such a result to
   MSPI_REQUIRE(H >= 6 && W >= 6, "mspi_postprocess_u8: a %d x %d map is smaller than the blur radius (H, W >= 6): no reference "
                "defines the result", H, W);
-  static bool init = false;
-  if (!init) {   // cv2.getGaussianKernel(11, sigma = 0.3*((11-1)*0.5-1)+0.8 = 2.0)
-    float k[11], s = 0.f;
-    for (int i = 0; i < 11; ++i) { k[i] = expf(-(float)((i - 5) * (i - 5)) / (2.f * 2.0f * 2.0f)); s += k[i]; }
-    for (int i = 0; i < 11; ++i) k[i] /= s;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(c_gauss11), k, sizeof(k)) != hipSuccess) {
-      set_error("mspi_postprocess_u8: cannot upload the Gaussian kernel");
-      (void)hipGetLastError();
-      return MSPI_ELAUNCH;
-    }
-    init = true;
-  }
+  // cv2.getGaussianKernel(11, sigma = 0.3*((11-1)*0.5-1)+0.8 = 2.0), computed on the host in every call: the entry point
+  // keeps no state, so its first call of a process is as capturable as any other, on any device and any thread
+  Gauss11 g;
+  float gsum = 0.f;
+  for (int i = 0; i < 11; ++i) { g.k[i] = expf(-(float)((i - 5) * (i - 5)) / (2.f * 2.0f * 2.0f)); gsum += g.k[i]; }
+  for (int i = 0; i < 11; ++i) g.k[i] /= gsum;
   hipStream_t s = (hipStream_t)stream;
   MSPI_REQUIRE(aligned16(workspace), "mspi_postprocess_u8: workspace must be 16-byte aligned");
   float* blurred = reinterpret_cast<float*>(workspace);
@@ -166,7 +165,7 @@ extern "C" int mspi_postprocess_u8(const float* logmap, unsigned char* out, void
   const int nb = (Ho * Wo + 255) / 256;
   float* part = resized + pp_r4((size_t)N * Ho * Wo);
   float* mm = part + pp_r4((size_t)N * 2 * nb);
-  hipLaunchKernelGGL(blur_exp_kernel, dim3((H * W + 255) / 256, N), dim3(256), 0, s, logmap, blurred, H, W);
+  hipLaunchKernelGGL(blur_exp_kernel, dim3((H * W + 255) / 256, N), dim3(256), 0, s, logmap, blurred, H, W, g);
   hipLaunchKernelGGL(resize_minmax_kernel, dim3(nb, N), dim3(256), 0, s, blurred, resized, H, W, Ho, Wo, part, g_status_word);
   hipLaunchKernelGGL(minmax_reduce_kernel, dim3(N), dim3(256), 0, s, part, nb, mm);
   hipLaunchKernelGGL(quantize_kernel, dim3((Ho * Wo + 4095) / 4096, N), dim3(256), 0, s, resized, mm, out, Ho * Wo);

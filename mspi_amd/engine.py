@@ -157,6 +157,10 @@ def _stream():
 def _need_gpu(t):
     if not t.is_cuda:
         raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % t.device)
+    cur = torch.cuda.current_device()
+    if t.device.index != cur:      # _stream() hands every launch the current stream of the CURRENT device
+        raise MspiError("tensor on %s, but the current device is cuda:%d: the launch would go to the wrong device's stream; "
+                        "call under torch.cuda.device(%d)" % (t.device, cur, t.device.index))
     if _STATUS["word"] is None:
         _register_status_word()
 

@@ -207,6 +207,19 @@ def test_frame_feature_cache(dev, tmp_path):
     a = model(clips, aud)[0]
     b = model(clips, aud, frame_feats=(f1[flat], f0[flat]))[0]
     assert (a - b).abs().max().item() < 1e-5
+    # the clip loop's runner returns u8 maps; the fp32 map in front of its post-processing, replayed from the runner's kind of
+    # pipeline (hipGraphs of the cached-frames forward, two in flight), is the eager forward of the same windows bit for bit
+    from mspi_amd.runtime import GraphPipeline
+    ff = (f1[flat], f0[flat])
+    b = b.clone()
+    pipe = GraphPipeline(lambda c, s, g1, g0: model(c, s, frame_feats=(g1, g0))[0], (clips, aud) + ff, depth=2, layouts=1, watch=model)
+    rev = (clips.flip(0), aud.flip(0)) + tuple(t.view(3, 16, *t.shape[1:]).flip(0).reshape(t.shape) for t in ff)      # windows in reverse order
+    b_rev = model(rev[0], rev[1], frame_feats=rev[2:])[0].clone()
+    tickets = [pipe.submit(clips, aud, *ff), pipe.submit(*rev)]
+    assert torch.equal(pipe.fetch(tickets[0]), b) and torch.equal(pipe.fetch(tickets[1]), b_rev)
+    assert not torch.equal(b, b_rev)
+    pipe.drain()
+    del pipe
     out = {}
     for tag, cache, graph in (("cached", True, True), ("plain", False, True), ("eager", True, False)):
         args = types.SimpleNamespace(clip_size=16, dataset="TOY", split=2, path_data=root, save_path=str(tmp_path / tag),
