@@ -274,6 +274,15 @@ _SIGNATURES = {
 
 EXPORTS = tuple(_SIGNATURES)
 
+# The training entry points declared in include/mspi_train_hip.h: same library, a table of their own (the header says why)
+_TRAIN_SIGNATURES = {
+    "mspi_rowgate_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
+    "mspi_upsample_sum_bwd": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, _P]),
+}
+
+TRAIN_EXPORTS = tuple(_TRAIN_SIGNATURES)
+
 _lib = None
 
 
@@ -292,7 +301,7 @@ def load():
     # ROCm-capable device is detected" (seen when build() loaded the library before anything had imported torch).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

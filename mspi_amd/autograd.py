@@ -6,7 +6,11 @@ Forward and backward run on the C ABI (mspi_amd.engine); the forward launches wh
 
 ReadoutHead: the three convs in front of it (readout[0], readout[1] + BatchNorm readout[2], readout[4] + BatchNorm readout[5],
 model/model_utils.py:490-497) with the BatchNorm layers on BATCH statistics, over the four fused pyramid maps.  Its output is
-ReadoutTail's input, so the two together train the whole readout Sequential."""
+ReadoutTail's input, so the two together train the whole readout Sequential.
+
+Fusion: the stage in front of that -- the three SA gates (model/model_utils.py:155-170) with their BatchNorm on BATCH
+statistics and the top-down sums of model/model_utils.py:566-567 -- over the four lateral outputs and the adapter's masks.  Its
+outputs are ReadoutHead's maps, whose gradients ReadoutHead computes when they are asked for."""
 import torch
 
 from . import engine as E
@@ -103,16 +107,21 @@ def r0_parts(weight, bias):
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1          # nn.BatchNorm3d's defaults, which the readout's two layers are built with
 
 
+def _bn_running(buffers, mean, var, M, momentum):
+    """The running-stat update of nn.BatchNorm3d.train(): the UNBIASED variance into running_var, num_batches_tracked += 1."""
+    rm, rv, nbt = buffers
+    rm.mul_(1.0 - momentum).add_(mean, alpha=momentum)
+    rv.mul_(1.0 - momentum).add_(var, alpha=momentum * M / (M - 1.0))
+    nbt.add_(1)
+
+
 def _bn_train(x, gamma, beta, buffers):
-    """BatchNorm on batch statistics + ReLU, and the running-stat update of nn.BatchNorm3d.train(): momentum 0.1, the
-    UNBIASED variance into running_var, num_batches_tracked += 1.  Returns (y, mean, rstd)."""
+    """BatchNorm on batch statistics + ReLU, and the running-stat update of nn.BatchNorm3d.train() with momentum 0.1 (buffers
+    None: skipped).  Returns (y, mean, rstd)."""
     mean, var, rstd = E.bn_stats(x, BN_EPS)
     y = E.bn_apply(x, mean, rstd, gamma.detach().contiguous(), beta.detach().contiguous(), act=E.ACT_RELU)
     if buffers is not None:
-        rm, rv, nbt = buffers
-        rm.mul_(1.0 - BN_MOMENTUM).add_(mean, alpha=BN_MOMENTUM)
-        rv.mul_(1.0 - BN_MOMENTUM).add_(var, alpha=BN_MOMENTUM * x.M / (x.M - 1.0))
-        nbt.add_(1)
+        _bn_running(buffers, mean, var, x.M, BN_MOMENTUM)
     return y, mean, rstd
 
 
@@ -129,7 +138,8 @@ class ReadoutHead(torch.autograd.Function):
     bn2 / bn5: (running_mean, running_var, num_batches_tracked) of readout[2] / readout[5], updated in place as
     nn.BatchNorm3d.train() updates them; None only skips that update -- the normalisation is on BATCH statistics either way,
     never on the running ones (the model refuses a grad forward with these two modules in eval()).  Returns y4 [B,T,h,w,C4], the input of ReadoutTail.
-    Gradients: the ten parameters.  The maps get none: everything in front of the readout is frozen.  No double backward."""
+    Gradients: the ten parameters, and each of the four maps that requires grad (d s0 = W0^T dy0, d sj = (W0 + Wj)^T up_j^T dy0:
+    four more 1x1x1 convs); with detached maps nothing more is launched than before.  No double backward."""
 
     @staticmethod
     def forward(ctx, s0, s1, s2, s3, w0, b0, w1, b1, g2, be2, w4, b4, g5, be5, bn2, bn5):
@@ -153,14 +163,14 @@ class ReadoutHead(torch.autograd.Function):
             a1, m2, r2 = _bn_train(x1, g2, be2, bn2)
             x4 = E.conv(a1, pk4)
             y4, m5, r5 = _bn_train(x4, g5, be5, bn5)
-        ctx.save_for_backward(*maps, y0.buf, x1.buf, a1.buf, x4.buf, y4.buf, m2, r2, m5, r5, w1, g2, w4, g5)
+        ctx.save_for_backward(*maps, y0.buf, x1.buf, a1.buf, x4.buf, y4.buf, m2, r2, m5, r5, w1, g2, w4, g5, w0, b0)
         ctx.packs = (parts, pk1, pk4)
         return y4.buf.view(y4.N, y4.T, y4.H, y4.W, y4.ld)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        s0, s1, s2, s3, y0b, x1b, a1b, x4b, y4b, m2, r2, m5, r5, w1, g2, w4, g5 = ctx.saved_tensors
+        s0, s1, s2, s3, y0b, x1b, a1b, x4b, y4b, m2, r2, m5, r5, w1, g2, w4, g5, w0, b0 = ctx.saved_tensors
         parts, pk1, pk4 = ctx.packs
         B, T, h, w, D = s0.shape
         c1, c4 = w1.shape[0], w4.shape[0]
@@ -180,8 +190,160 @@ class ReadoutHead(torch.autograd.Function):
         # and <up_j(A s), dy0> = <A s, up_j^T dy0>, so with g_j = up_j^T dy0 (upsample_bwd) and G0 = dy0^T s0, G_j = g_j^T sj':
         #   dL/dW0 = G0 + G1 + G2 + G3 (W0 takes part in every term), dL/dWj = G_j, db0 = sum dy0
         G0, db0 = E.conv_wgrad_wide(_cl5(s0), dy0, parts[0])
-        Gs = [E.conv_wgrad_wide(_cl5(s), E.upsample_bwd(dy0, k), pk)[0] for s, k, pk in ((s1, 2, parts[1]), (s2, 4, parts[2]), (s3, 8, parts[3]))]
+        gs = [dy0] + [E.upsample_bwd(dy0, k) for k in (2, 4, 8)]
+        Gs = [E.conv_wgrad_wide(_cl5(s), g, pk)[0] for s, g, pk in ((s1, gs[1], parts[1]), (s2, gs[2], parts[2]), (s3, gs[3], parts[3]))]
         dw0 = torch.cat([((G0 + Gs[0]) + Gs[1]) + Gs[2]] + Gs, dim=1)
-        grads = [None] * 4 + [dw0, db0, dw1, db1, dg2, dbe2, dw4, db4, dg5, dbe5, None, None]
         need = ctx.needs_input_grad
+        # the maps' gradients, each only when asked for: d s0 = W0^T dy0, d sj = (W0 + Wj)^T g_j -- the transposed 1x1x1 part on
+        # the fp32 MFMA path, its operand being a gradient at the loss's scale (ReadoutTail.backward)
+        dmaps = [None] * 4
+        for j, (wj, _) in enumerate(r0_parts(w0, b0)):
+            if need[j]:
+                d = E.conv(gs[j], E.pack_conv(wj.t().contiguous(), None, prec=E.PREC_F32))
+                dmaps[j] = d.buf.view(d.N, d.T, d.H, d.W, d.ld)
+        grads = dmaps + [dw0, db0, dw1, db1, dg2, dbe2, dw4, db4, dg5, dbe5, None, None]
         return tuple(gr if need[i] else None for i, gr in enumerate(grads))
+
+
+SA_BN_EPS, SA_BN_MOMENTUM = 1e-3, 0.001  # BasicConv3d's BatchNorm3d(eps=1e-3, momentum=0.001) (backbones/s3d.py:45), SA's first layer
+SA_FACTORS = (4, 2, 1)                   # sa_0, sa_1, sa_2 up-sample their premask by these (model/model_utils.py:500-502 upstream)
+WGRAD_WIDE_MAX_CH = 192                  # widest stored channel count mspi_conv_wgrad_wide_fwd takes
+
+
+def _geometry(k, pad, cin, cout):
+    """What conv_wgrad_wide reads of a pack (the layer's geometry), without packing any weights."""
+    p = E.PackedConv()
+    p.k, p.stride, p.pad, p.cin, p.cin_s, p.cout, p.cout_s = k, (1, 1, 1), pad, cin, cin, cout, cout
+    return p
+
+
+class Fusion(torch.autograd.Function):
+    """s0, s1, s2, s3 = Fusion.apply(l0, l1, l2, l3, masks, *sa, bn_0, bn_1, bn_2): the decoder stage between the laterals and
+    readout[0] -- the three SA gates (model/model_utils.py:155-170) and the top-down sums of model/model_utils.py:566-567 -- as
+    the default path of _SaliencyBase._fuse_readout runs it, returning the four maps autograd.ReadoutHead takes.
+    l0..l3: the lateral outputs, channels-last fp32 [B,T,h,w,D] .. [B,T,h/8,w/8,D]; masks: the adapter's [B,T,h/4,w/4,Cm].
+    sa: for k = 0, 1, 2 (sa_0 gates l0 after a x4 up-sample, sa_1 l1 after x2, sa_2 l2) the five tensors conv_mask[0].conv.weight,
+    conv_mask[0].bn.weight, conv_mask[0].bn.bias, conv_mask[2].weight, conv_mask[2].bias in their nn layouts.  bn_k:
+    (running_mean, running_var, num_batches_tracked) of sa_k.conv_mask[0].bn, updated in place as nn.BatchNorm3d.train()
+    with that layer's momentum 0.001 updates them, or None to skip that; the normalisation is on BATCH statistics either way.
+    Gradients: the 15 SA tensors and each lateral that requires grad; masks gets none (the adapter is frozen).  No double
+    backward."""
+
+    @staticmethod
+    def forward(ctx, l0, l1, l2, l3, masks, *rest):
+        if len(rest) != 18:
+            raise MspiError("Fusion: expected 15 SA tensors and 3 BatchNorm buffer triples after masks, got %d arguments" % len(rest))
+        sa, bns = [rest[5 * k:5 * k + 5] for k in range(3)], rest[15:]
+        lats = []
+        for j, t in enumerate((l0, l1, l2, l3)):
+            if not t.is_cuda:
+                raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % t.device)
+            if t.dim() != 5 or t.dtype != torch.float32 or t.shape[4] != l0.shape[4] or t.shape[4] % 4 or t.shape[:2] != l0.shape[:2] or \
+                    (t.shape[2] << j, t.shape[3] << j) != tuple(l0.shape[2:4]):
+                raise MspiError("Fusion: l%d %s does not continue the pyramid of l0 %s (fp32 channels-last, a multiple of 4 wide, "
+                                "each level half the one before)" % (j, tuple(t.shape), tuple(l0.shape)))
+            lats.append(t.detach().contiguous())
+        B, T, h, w, D = l0.shape
+        mid, Cm = sa[0][0].shape[:2]
+        if masks.dim() != 5 or masks.dtype != torch.float32 or tuple(masks.shape) != (B, T, h // 4, w // 4, Cm) or masks.device != l0.device:
+            raise MspiError("Fusion: masks %s is not fp32 [B,T,h/4,w/4,%d] on the level of l2" % (tuple(masks.shape), Cm))
+        for k, (wc, gam, bet, w2, b2) in enumerate(sa):
+            if tuple(wc.shape) != (mid, Cm, 3, 3, 3) or gam.numel() != mid or bet.numel() != mid or tuple(w2.shape) != (1, mid, 1, 3, 3) or \
+                    b2.numel() != 1 or mid % 32 or Cm % 32:
+                raise MspiError("Fusion: the tensors of sa_%d are not a (3,3,3) conv %d -> %d (multiples of 32), its BatchNorm and a "
+                                "(1,3,3) conv to 1" % (k, Cm, mid))
+        masks = masks.detach().contiguous()
+        with torch.no_grad():
+            x = _cl5(masks)
+            # the three first convs share their input: one conv Cm -> 3 mid, unfolded (no bias, no activation), then one BatchNorm
+            pre = E.conv(x, E.pack_conv(torch.cat([p[0] for p in sa], 0), None, None, (1, 1, 1), (1, 1, 1), E.ACT_NONE))
+            gamma = torch.cat([p[1].detach().float() for p in sa]).contiguous()
+            beta = torch.cat([p[2].detach().float() for p in sa]).contiguous()
+            mean, var, rstd = E.bn_stats(pre, SA_BN_EPS)
+            pm = E.bn_apply(pre, mean, rstd, gamma, beta, act=E.ACT_RELU)
+            for k, bn in enumerate(bns):
+                if bn is not None:
+                    _bn_running(bn, mean[k * mid:(k + 1) * mid], var[k * mid:(k + 1) * mid], pre.M, SA_BN_MOMENTUM)
+            outs, ms, gates = [], [], []
+            for k in (2, 1, 0):                       # the order of _fuse_readout
+                m = pm.slice(k * mid, mid)
+                if SA_FACTORS[k] != 1:
+                    m = E.upsample(m, SA_FACTORS[k])
+                gate = E.conv(m, E.pack_conv(sa[k][3], sa[k][4], None, (1, 1, 1), (0, 1, 1), E.ACT_SIGMOID))
+                s = _cl5(lats[k].clone())             # the ungated l_k is what the backward reads
+                E.rowgate(s, gate)
+                if k == 2:
+                    E.upsample(_cl5(lats[3]), 2, dst=s, accumulate=True)
+                elif k == 1:
+                    E.upsample_sum(s, [(outs[0], 2), (_cl5(lats[3]), 4)])
+                outs.append(s)
+                ms.append(m.buf)
+                gates.append(gate.buf)
+        s2, s1, s0 = outs
+        ctx.save_for_backward(lats[0], lats[1], lats[2], masks, pre.buf, pm.buf, mean, rstd, gamma, *ms[::-1], *gates[::-1],
+                              *[p[3] for p in sa])
+        ctx.dims = (B, T, h, w, D, Cm, mid)
+        return tuple(t.buf.view(t.N, t.T, t.H, t.W, t.ld) for t in (s0, s1, s2)) + (lats[3].clone(),)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G0, G1, G2, G3):
+        l0, l1, l2, masks, preb, pmb, mean, rstd, gamma, m0b, m1b, m2b, g0b, g1b, g2b, w20, w21, w22 = ctx.saved_tensors
+        B, T, h, w, D, Cm, mid = ctx.dims
+        need = ctx.needs_input_grad
+        dev = l0.device
+        hm, wm = h // 4, w // 4
+
+        def grad(g, j):        # the incoming gradients are read only: an absent one is a zero map
+            shape = (B, T, h >> j, w >> j, D)
+            return _cl5(torch.zeros(shape, dtype=torch.float32, device=dev) if g is None else g.float().contiguous())
+        G = [grad(g, j) for j, g in enumerate((G0, G1, G2, G3))]
+        # s2 = gate(l2) + up2(l3), s1 = gate(l1) + up2(s2) + up4(l3):  D2 = G2 + up2^T G1,  D3 = G3 + up4^T G1 + up2^T D2
+        D2 = E.upsample_sum_bwd(_cl5(G[2].buf.view(B, T, h >> 2, w >> 2, D).clone()), [(G[1], 2)], accumulate=True)
+        grads = [None] * 23
+        if need[3]:
+            D3 = E.upsample_sum_bwd(_cl5(G[3].buf.view(B, T, h >> 3, w >> 3, D).clone()), [(G[1], 4), (D2, 2)], accumulate=True)
+            grads[3] = D3.buf.view(B, T, h >> 3, w >> 3, D)
+        sa_need = any(need[5:20])
+        dp = E.alloc(B, T, hm, wm, 3 * mid, dev)
+        for k, (Gk, lk, mb, gb, w2) in enumerate(((G[0], l0, m0b, g0b, w20), (G[1], l1, m1b, g1b, w21), (D2, l2, m2b, g2b, w22))):
+            if not (need[k] or sa_need):
+                continue
+            f = SA_FACTORS[k]
+            hk, wk = h >> k, w >> k
+            dl, dz = E.rowgate_bwd(Gk, _cl5(lk), E.CL(gb, 0, B, T, hk, wk, 1, 1), need_dx=need[k])
+            if need[k]:
+                grads[k] = dl.buf.view(B, T, hk, wk, D)
+            if not sa_need:
+                continue
+            # mspi_conv_c1_bwd masks its data gradient where its input y <= 0, and that is exact for all three gates.  sa_2
+            # (f == 1): y is the post-ReLU premask, so the mask is the ReLU's.  sa_0, sa_1: y is a bilinear up-sample, with
+            # non-negative weights, of the non-negative premask; it is 0 only where every source it taps with a positive weight
+            # is 0, the gradient of such a cell goes to those sources alone, and bn_bwd's ReLU mask clears them anyway.
+            # (T folds into N: a (1,3,3) conv does not mix frames.)
+            m = E.CL(mb, 0, B * T, 1, hk, wk, mid, mid) if f != 1 else E.CL(mb, k * mid, B * T, 1, hk, wk, mid, 3 * mid)
+            dm, dw2, db2 = E.conv_c1_bwd(m, dz.view(B * T, hk, wk), w2)
+            grads[5 + 5 * k + 3], grads[5 + 5 * k + 4] = dw2, db2
+            if f != 1:
+                E.upsample_bwd(dm.reshape(B, T, hk, wk), f, dx=dp.slice(k * mid, mid))
+            else:
+                dp.buf.view(-1, 3 * mid)[:, k * mid:(k + 1) * mid].copy_(dm.buf.view(-1, mid))
+        if not sa_need:
+            return tuple(grads)
+        pre, pm = E.CL(preb, 0, B, T, hm, wm, 3 * mid, 3 * mid), E.CL(pmb, 0, B, T, hm, wm, 3 * mid, 3 * mid)
+        dpre, dgam, dbet = E.bn_bwd(dp, pre, mean, rstd, gamma, y=pm)
+        # the (3,3,3) conv's weight gradient in input-channel slices the wide kernel takes (512 = 192 + 192 + 128): a slice of
+        # the wider tensor as it stands where the kernel accepts its strides, a dense copy where it refuses
+        x = _cl5(masks)
+        parts = []
+        for c0 in range(0, Cm, WGRAD_WIDE_MAX_CH):
+            c = min(WGRAD_WIDE_MAX_CH, Cm - c0)
+            xs, geo = x.slice(c0, c), _geometry((3, 3, 3), (1, 1, 1), c, 3 * mid)
+            if E.conv_wgrad_wide_variant(xs, dpre, geo) < 0:
+                xs = _cl5(masks[..., c0:c0 + c].contiguous())
+            parts.append(E.conv_wgrad_wide(xs, dpre, geo)[0])
+        dW = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+        for k in range(3):
+            sl = slice(k * mid, (k + 1) * mid)
+            grads[5 + 5 * k], grads[5 + 5 * k + 1], grads[5 + 5 * k + 2] = dW[sl], dgam[sl], dbet[sl]
+        return tuple(g if g is None or need[i] else None for i, g in enumerate(grads))

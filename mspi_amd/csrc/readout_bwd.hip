@@ -10,6 +10,7 @@
 // adds them in a fixed order: no float atomics, bitwise repeatable.  Nothing here allocates or synchronises.
 #include "common.h"
 #include "conv_common.h"
+#include "upsample_adjoint.h"
 
 namespace mspi {
 
@@ -266,30 +267,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------ up-sample adjoint
-// Gather form of upsample_kernel's adjoint: source cell (h, w) collects the destination cells whose two taps per axis
-// (h0, h1 = min(h0 + 1, H - 1), weights 1 - lh, lh; align_corners=False, clamped at 0) include it: for an even factor k
-// those are ho in [k h - k / 2, k h + 3 k / 2), clipped to the image.  Factors 2, 4, 8 make every weight a dyadic fraction.
-template <int K>
-__device__ __forceinline__ void up_axis_weights(int h, int H, float (&wt)[2 * K]) {
-  const float inv = 1.f / (float)K;
-#pragma unroll
-  for (int j = 0; j < 2 * K; ++j) {
-    const int ho = K * h - K / 2 + j;
-    float f = ((float)ho + 0.5f) * inv - 0.5f;
-    f = f < 0.f ? 0.f : f;
-    const int h0 = (int)f;
-    const int h1 = h0 + (h0 < H - 1 ? 1 : 0);
-    const float l = f - (float)h0;
-    float v = 0.f;
-    if (ho >= 0 && ho < K * H) v = (h0 == h ? 1.f - l : 0.f) + (h1 == h ? l : 0.f);
-    wt[j] = v;
-  }
-}
-
+// Gather form of upsample_kernel's adjoint (up_gather, upsample_adjoint.h): one thread per source vector.
 template <int K, bool RELU>
 __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restrict__ dy, long ldy, const float* __restrict__ u,
                                                            long ldu, float* __restrict__ dx, long ldx, int NT, int H, int W, int CV) {
-  const int Ho = H * K, Wo = W * K;
   const long total = (long)NT * H * W * CV;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;      // one source vector per thread (fewer than 2^31, host-checked)
   if (idx < total) {
@@ -300,29 +281,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
     pos /= (unsigned)W;
     const int h = (int)(pos % (unsigned)H);
     const long nt = (long)(pos / (unsigned)H);
-    float wh[2 * K], ww[2 * K];
-    up_axis_weights<K>(h, H, wh);
-    up_axis_weights<K>(w, W, ww);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int jh = 0; jh < 2 * K; ++jh) {
-      const int ho = K * h - K / 2 + jh;
-      if (ho < 0 || ho >= Ho) continue;
-#pragma unroll
-      for (int jw = 0; jw < 2 * K; ++jw) {
-        const int wo = K * w - K / 2 + jw;
-        if (wo < 0 || wo >= Wo) continue;
-        const long row = (nt * Ho + ho) * Wo + wo;
-        float4 gv = *reinterpret_cast<const float4*>(dy + row * ldy + cv * 4);
-        if (RELU) {
-          const float4 uv = *reinterpret_cast<const float4*>(u + row * ldu + cv * 4);
-          gv.x = uv.x > 0.f ? gv.x : 0.f; gv.y = uv.y > 0.f ? gv.y : 0.f;
-          gv.z = uv.z > 0.f ? gv.z : 0.f; gv.w = uv.w > 0.f ? gv.w : 0.f;
-        }
-        const float c = wh[jh] * ww[jw];
-        acc.x = fmaf(c, gv.x, acc.x); acc.y = fmaf(c, gv.y, acc.y); acc.z = fmaf(c, gv.z, acc.z); acc.w = fmaf(c, gv.w, acc.w);
-      }
-    }
+    const float4 acc = up_gather<K, RELU>(dy, ldy, u, ldu, nt, h, w, H, W, cv);
     *reinterpret_cast<float4*>(dx + ((nt * H + h) * W + w) * ldx + cv * 4) = acc;
   }
 }

@@ -25,7 +25,7 @@ from .packs import (DEFAULT_PREC, SP_ENABLED, PackedConv, PackedDw, PackedMlp, P
 __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedConv", "PackedDw", "conv", "dwconv", "maxpool",
            "layernorm", "attention", "upsample", "upsample_sum", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine", "se_gate",
            "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "conv_wgrad_wide",
-           "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "rowgate_bwd", "upsample_sum_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 # ----------------------------------------------------------------------------- conv autotuning
@@ -1111,9 +1111,9 @@ def conv_wgrad(x, dy, pk):
     return dW[:pk.cout, :, :, :, :pk.cin].permute(0, 4, 1, 2, 3), db[:pk.cout]
 
 
-def upsample_bwd(dy, factor, u=None, act=ACT_NONE):
+def upsample_bwd(dy, factor, u=None, act=ACT_NONE, dx=None):
     """Adjoint of upsample(src, factor, act=act): dy is the gradient of the up-sampled CL; with act == ACT_RELU, u is the
-    forward's output and supplies the ReLU mask.  Returns the gradient of src."""
+    forward's output and supplies the ReLU mask.  Returns the gradient of src: a new CL, or dx (e.g. a channel slice)."""
     lib = _lib.load()
     _need_gpu(dy.buf)
     if factor not in (2, 4, 8) or dy.H % factor or dy.W % factor or not dy.dense:
@@ -1122,7 +1122,10 @@ def upsample_bwd(dy, factor, u=None, act=ACT_NONE):
         raise MspiError("upsample_bwd: act is ACT_NONE without u, or ACT_RELU with the forward's output u")
     if u is not None and ((u.N, u.T, u.H, u.W, u.Cs) != (dy.N, dy.T, dy.H, dy.W, dy.Cs) or not u.dense or u.buf.device != dy.buf.device):
         raise MspiError("upsample_bwd: u does not match the gradient")
-    dx = alloc(dy.N, dy.T, dy.H // factor, dy.W // factor, dy.C, dy.buf.device)
+    if dx is None:
+        dx = alloc(dy.N, dy.T, dy.H // factor, dy.W // factor, dy.C, dy.buf.device)
+    elif (dx.N, dx.T, dx.H, dx.W, dx.C) != (dy.N, dy.T, dy.H // factor, dy.W // factor, dy.C) or not dx.dense or dx.buf.device != dy.buf.device:
+        raise MspiError("upsample_bwd: dx does not match the gradient divided by the factor")
     with _Timed("upsample_bwd", 0.0, 4.0 * (dx.M + dy.M * (2 if u is not None else 1)) * dy.C):
         check(lib.mspi_upsample_bwd(dy.ptr, dy.ld, u.ptr if u is not None else None, u.ld if u is not None else 0, dx.ptr, dx.ld,
                                     dy.N * dy.T, dx.H, dx.W, dy.Cs, factor, act, _stream()), "mspi_upsample_bwd")
@@ -1227,6 +1230,59 @@ def bn_bwd(dy, x, mean, rstd, gamma, y=None):
                               ptrs[0], ptrs[1], ptrs[2], dx.ptr, dx.ld, dgb[0].data_ptr(), dgb[1].data_ptr(), ws.data_ptr(),
                               M, Cc, _stream()), "mspi_bn_bwd")
     return dx, dgb[0], dgb[1]
+
+
+# ----------------------------------------------------------------------------- SA gating / fusion backward (csrc/fusion_bwd.hip)
+def rowgate_bwd(dy, x, gate, need_dx=True):
+    """Backward of rowgate(x, gate): dy the gradient of the gated rows, x the UNGATED input, gate the CL [.., 1] of sigmoids.
+    Returns (dx, dz): dx = dy (1 + gate), a new CL like dy (None with need_dx=False); dz [M] fp32, the gradient of the logit in
+    front of the sigmoid."""
+    lib = _lib.load()
+    _need_gpu(dy.buf)
+    dev = dy.buf.device
+    if not dy.dense or not x.dense or (x.M, x.Cs) != (dy.M, dy.Cs) or dy.Cs != dy.C or x.buf.device != dev:
+        raise MspiError("rowgate_bwd: dy (%d rows x %d) and x (%d rows x %d) must be dense, alike and a multiple of 4 wide"
+                        % (dy.M, dy.C, x.M, x.C))
+    if gate.M != dy.M or gate.ld != 1 or not gate.dense or gate.buf.device != dev:
+        raise MspiError("rowgate_bwd: gate must hold one value per row (%d rows, ld 1), got %d rows, ld %d" % (dy.M, gate.M, gate.ld))
+    dx = alloc(dy.N, dy.T, dy.H, dy.W, dy.C, dev) if need_dx else None
+    dz = torch.empty(dy.M, dtype=torch.float32, device=dev)
+    with _Timed("rowgate_bwd", 2.0 * dy.M * dy.C, 4.0 * dy.M * (dy.C * (3 if need_dx else 2) + 2), "M=%d C=%d" % (dy.M, dy.C)):
+        check(lib.mspi_rowgate_bwd(dy.ptr, dy.ld, x.ptr, x.ld, gate.ptr, dx.ptr if need_dx else None, dx.ld if need_dx else 0,
+                                   dz.data_ptr(), dy.M, dy.Cs, _stream()), "mspi_rowgate_bwd")
+    return dx, dz
+
+
+def upsample_sum_bwd(dx, srcs, accumulate=False):
+    """Adjoint of upsample_sum: dx (= or +=) sum of the up-sample adjoints of srcs = [(CL gradient, factor 2 | 4 | 8), ...], at
+    most three, in one pass over dx.  dx None: a new CL (accumulate must be off).  Returns dx."""
+    lib = _lib.load()
+    J = len(srcs)
+    if not 1 <= J <= 3:
+        raise MspiError("upsample_sum_bwd: 1 to 3 sources, got %d" % J)
+    g0, k0 = srcs[0]
+    _need_gpu(g0.buf)
+    dev = g0.buf.device
+    if k0 not in (2, 4, 8) or g0.H % k0 or g0.W % k0:
+        raise MspiError("upsample_sum_bwd: factor %s must be 2, 4 or 8 and divide the gradient's %d x %d" % (k0, g0.H, g0.W))
+    if dx is None:
+        if accumulate:
+            raise MspiError("upsample_sum_bwd: accumulate needs the dx to add to")
+        dx = alloc(g0.N, g0.T, g0.H // k0, g0.W // k0, g0.C, dev)
+    if not dx.dense or dx.Cs != dx.C or dx.buf.device != dev:
+        raise MspiError("upsample_sum_bwd: dx must be dense, a multiple of 4 wide and on %s" % dev)
+    for g, k in srcs:
+        if k not in (2, 4, 8) or not g.dense or g.buf.device != dev or (g.N, g.T, g.H, g.W, g.C) != (dx.N, dx.T, dx.H * k, dx.W * k, dx.C):
+            raise MspiError("upsample_sum_bwd: a dense gradient [%d,%d,%d,%d,%d] with factor %s is not factor (2, 4 or 8) times dx "
+                            "[%d,%d,%d,%d,%d]" % (g.N, g.T, g.H, g.W, g.C, k, dx.N, dx.T, dx.H, dx.W, dx.C))
+    ptrs = (C.c_void_p * J)(*[g.ptr for g, _ in srcs])
+    lds = (C.c_int64 * J)(*[g.ld for g, _ in srcs])
+    ks = (C.c_int32 * J)(*[k for _, k in srcs])
+    with _Timed("upsample_sum_bwd", 0.0, 4.0 * (sum(g.M for g, _ in srcs) + dx.M * (2 if accumulate else 1)) * dx.C,
+                "M=%d C=%d k=%s" % (dx.M, dx.C, ",".join(str(k) for _, k in srcs))):
+        check(lib.mspi_upsample_sum_bwd(ptrs, lds, ks, J, dx.ptr, dx.ld, dx.N * dx.T, dx.H, dx.W, dx.Cs, 1 if accumulate else 0,
+                                        _stream()), "mspi_upsample_sum_bwd")
+    return dx
 
 
 def mean_rows(x, N, R, out):

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from .. import engine as E
 from .._lib import MspiError
-from ..autograd import ReadoutHead, ReadoutTail, pack_readout_tail, r0_parts, readout_tail_forward
+from ..autograd import Fusion, ReadoutHead, ReadoutTail, pack_readout_tail, r0_parts, readout_tail_forward
 from ..backbones.convnext import ConvNeXtTinyFeatures
 from ..backbones.resnet import get_resnet18
 from ..module import HipModule, to_cl
@@ -429,11 +429,8 @@ class _SaliencyBase(HipModule):
 
     def _pack_decoder(self, split=None):
         r = self.readout
-        # sa_0/1/2.conv_mask[0] are three 3x3x3 convs 512->32 over the SAME masks tensor: one conv 512->96
-        sa_w, sa_b = zip(*[E.fold_bn(m.conv_mask[0].conv.weight, None, m.conv_mask[0].bn) for m in (self.sa_0, self.sa_1, self.sa_2)])
-        sa_cat = E.pack_conv(torch.cat(sa_w, 0), torch.cat(sa_b, 0), None, (1, 1, 1), (1, 1, 1), E.ACT_RELU)
         return {
-            "sa_cat": sa_cat,
+            "sa_cat": self._pack_sa_cat(),
             "lat": [self._pack_lateral(k, split if k == 3 else None) for k in range(4)],
             "r0": E.pack_conv(r[0].weight, r[0].bias),
             "r0_parts": self._pack_r0_parts(r[0]),
@@ -444,7 +441,13 @@ class _SaliencyBase(HipModule):
             "r12": E.pack_conv(r[12].weight, r[12].bias, None, (1, 1, 1), (0, 1, 1), E.ACT_NONE),
             "tail_key": self._tail_key(),
             "head_key": self._head_key(),
+            "sa_key": self._sa_key(),
         }
+
+    def _pack_sa_cat(self):
+        """sa_0/1/2.conv_mask[0] are three 3x3x3 convs 512->32 over the SAME masks tensor: one conv 512->96."""
+        sa_w, sa_b = zip(*[E.fold_bn(m.conv_mask[0].conv.weight, None, m.conv_mask[0].bn) for m in (self.sa_0, self.sa_1, self.sa_2)])
+        return E.pack_conv(torch.cat(sa_w, 0), torch.cat(sa_b, 0), None, (1, 1, 1), (1, 1, 1), E.ACT_RELU)
 
     _r0_parts = staticmethod(r0_parts)      # the split of readout[0] over the coarse maps (autograd.r0_parts)
 
@@ -490,11 +493,14 @@ class _SaliencyBase(HipModule):
 
     def _premask(self, pk, masks):
         """The three SA modules' first convs (same input) as one 512->96 conv."""
+        self._refresh_sa(pk)
         return E.conv(masks, pk["sa_cat"])
 
     def _fuse_readout(self, pk, cat, s0, s1, s2, s3, masks, pm, features=False):
         """SA gating, top-down fusion and readout (model/model_utils.py:566-572); features=True stops in front of readout[8]
-        and returns y4 [B,4,h,w,64]."""
+        and returns y4 [B,4,h,w,64]; "maps" stops in front of readout[0]; "laterals" in front of the gating (pm is None then)."""
+        if features == "laterals":     # trainable("fusion"): autograd.Fusion takes over from here, then ReadoutHead
+            return s0, s1, s2, s3, masks
         if features != "maps":         # "maps": ReadoutHead packs the live values itself
             self._refresh_head(pk)
         self.sa_2.run(s2, masks, pm.slice(64, 32))
@@ -529,10 +535,16 @@ class _SaliencyBase(HipModule):
         self._refresh_tail(pk)
         return readout_tail_forward(y4, pk["r8"], pk["r10"], pk["r12"])[0]
 
-    # The readout trains (trainable()), so an optimiser moves it at every step: its packs follow the two keys below and are
-    # replaced one group at a time, and the plan's own key (module.HipModule.pk) leaves the readout's tensors out -- a step
-    # must not rebuild the laterals and the SA fold.
-    _PK_SELF_KEYED = ("readout",)
+    # The readout and the SA gates train (trainable()), so an optimiser moves them at every step: their packs follow the three
+    # keys below and are replaced one group at a time, and the plan's own key (module.HipModule.pk) leaves their tensors out --
+    # a step must not rebuild the laterals.  (The SA modules' own plans follow their own subtree keys.)
+    _PK_SELF_KEYED = ("readout", "sa_0", "sa_1", "sa_2")
+
+    def _refresh_sa(self, pk):
+        key = self._sa_key()
+        if pk["sa_key"] != key:        # an optimiser step, a training forward (running statistics) or a load has moved the SA fold
+            pk["sa_cat"] = self._pack_sa_cat()
+            pk["sa_key"] = key
 
     def _refresh_head(self, pk):
         key = self._head_key()
@@ -552,11 +564,18 @@ class _SaliencyBase(HipModule):
             pk["tail_key"] = key
 
     def _pk_refresh(self, pk):
-        """What a `pk` access outside a forward sees: the readout's packs at the present values, as the forward would make
-        them.  In a forward that carries a graph the head is left alone (ReadoutHead packs the live values itself)"""
+        """What a `pk` access outside a forward sees: the readout's packs and the SA fold at the present values, as the forward
+        would make them.  In a forward that carries a graph the head is left alone (ReadoutHead packs the live values itself)"""
         grad_tail = self._training_tail()
+        if [p for p, _ in self._sa_key()] != [p for p, _ in pk["sa_key"]]:
+            # an SA tensor lies in other storage than at pack time (.to(), .double().float() on the sub-module): not a training
+            # step, which writes in place.  As for any other sub-module, the whole plan is built again (`pk` packs when it is gone)
+            self.__dict__.pop("_pk", None)
+            return
         with torch.no_grad():
-            if grad_tail != "maps":
+            if grad_tail != "laterals":    # ... autograd.Fusion for the SA fold, whose premask that forward does not launch
+                self._refresh_sa(pk)
+            if grad_tail not in ("maps", "laterals"):
                 self._refresh_head(pk)
             if not grad_tail:          # ... and ReadoutTail does the same for the tail
                 self._refresh_tail(pk)
@@ -576,10 +595,24 @@ class _SaliencyBase(HipModule):
         ts += [t for i in (2, 5) for t in (r[i].weight, r[i].bias, r[i].running_mean, r[i].running_var)]
         return tuple((t.data_ptr(), t._version) for t in ts)
 
+    def _sa_key(self):
+        """The same for what sa_cat was built from: the first conv of each SA module and the affine parameters and running
+        statistics of the BatchNorm folded into it."""
+        ts = []
+        for m in (self.sa_0, self.sa_1, self.sa_2):
+            b = m.conv_mask[0]
+            ts += [b.conv.weight, b.bn.weight, b.bn.bias, b.bn.running_mean, b.bn.running_var]
+        return tuple((t.data_ptr(), t._version) for t in ts)
+
     TAIL_PARAMS = tuple("readout.%d.%s" % (i, n) for i in (8, 10, 12) for n in ("weight", "bias"))
 
     def trainable(self, what):
-        """trainable("readout"): the whole readout Sequential trains -- all 16 of its tensors get requires_grad, a forward with
+        """trainable("fusion"): the SA gates and the whole readout train -- the 15 tensors of sa_0, sa_1, sa_2 and the readout's
+        16 get requires_grad; a forward with grad enabled runs the encoders, the adapter and the laterals as in inference and
+        hands the four lateral outputs and the adapter's masks to autograd.Fusion (the three gates with their BatchNorm on BATCH
+        statistics, the top-down sums), then to autograd.ReadoutHead and autograd.ReadoutTail.  The laterals, the adapter and
+        every encoder stay frozen.
+        trainable("readout"): the whole readout Sequential trains -- all 16 of its tensors get requires_grad, a forward with
         grad enabled computes the four fused pyramid maps as in inference and hands them to autograd.ReadoutHead (readout[0],
         [1], [4] with readout[2] and [5] on BATCH statistics, which frozen_encoder() puts in train()) and then to
         autograd.ReadoutTail.  SA gating, the laterals, the fusion and every encoder stay frozen.
@@ -593,37 +626,57 @@ class _SaliencyBase(HipModule):
                 p.requires_grad_(flag)
             d["_trainable"] = None
             return self
-        if what not in ("readout_tail", "readout"):
-            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail' and 'readout' are)" % (what,))
-        if what == "readout" and not DECODER_FUSED:
-            raise MspiError("trainable('readout') needs the fused decoder path: it is switched off by MSPI_DECODER_FUSED=0")
+        if what not in ("readout_tail", "readout", "fusion"):
+            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail', 'readout' and 'fusion' are)"
+                            % (what,))
+        if what in ("readout", "fusion") and not DECODER_FUSED:
+            raise MspiError("trainable(%r) needs the fused decoder path: it is switched off by MSPI_DECODER_FUSED=0" % (what,))
         if d.get("_trainable") is None:
             d["_trainable_saved"] = [(p, p.requires_grad) for p in self.parameters()]
         d["_trainable"] = what
         tail = set(self.TAIL_PARAMS)
         for name, p in self.named_parameters():
-            p.requires_grad_(name.startswith("readout.") if what == "readout" else name in tail)
+            if what == "fusion":
+                p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.")))
+            else:
+                p.requires_grad_(name.startswith("readout.") if what == "readout" else name in tail)
         return self
+
+    def _batch_stat_modules(self):
+        """{name: module} of the BatchNorm layers that run on batch statistics under the present switch."""
+        what = self.__dict__.get("_trainable")
+        mods = {}
+        if what in ("readout", "fusion"):
+            mods.update({"readout.2": self.readout[2], "readout.5": self.readout[5]})
+        if what == "fusion":
+            mods.update({"sa_%d.conv_mask.0.bn" % k: getattr(self, "sa_%d" % k).conv_mask[0].bn for k in range(3)})
+        return mods
 
     def _training_tail(self):
         """What _forward stops at when this forward carries a graph: True (the features y4, for autograd.ReadoutTail), "maps"
-        (the four pyramid maps, for autograd.ReadoutHead and then ReadoutTail) or False."""
+        (the four pyramid maps, for autograd.ReadoutHead and then ReadoutTail), "laterals" (the lateral outputs and the masks,
+        for autograd.Fusion in front of those two) or False."""
         what = self.__dict__.get("_trainable")
         if what is None or not torch.is_grad_enabled():
             return False
-        return "maps" if what == "readout" else True
+        return {"readout": "maps", "fusion": "laterals"}.get(what, True)
 
     def _check_eval(self):
         """The forward's guard.  Under trainable("readout") exactly readout[2] and readout[5] may be in train() (they run on
-        batch statistics in autograd.ReadoutHead); any other module in train() is refused by name, as the model itself is."""
+        batch statistics in autograd.ReadoutHead), under trainable("fusion") also the three conv_mask[0].bn (autograd.Fusion);
+        any other module in train() is refused by name, as the model itself is."""
         super()._check_eval()
-        if self.__dict__.get("_trainable") != "readout":
+        what = self.__dict__.get("_trainable")
+        if what not in ("readout", "fusion"):
             return
-        allowed = {id(self.readout[2]), id(self.readout[5])}
+        allowed = {id(m) for m in self._batch_stat_modules().values()}
         for name, mod in self.named_modules():
             if mod.training and id(mod) not in allowed:
-                raise MspiError("%s.%s is in train() mode: under trainable('readout') only readout.2 and readout.5 run on batch "
-                                "statistics; call frozen_encoder()" % (type(self).__name__, name))
+                if what == "readout":
+                    raise MspiError("%s.%s is in train() mode: under trainable('readout') only readout.2 and readout.5 run on "
+                                    "batch statistics; call frozen_encoder()" % (type(self).__name__, name))
+                raise MspiError("%s.%s is in train() mode: under trainable('fusion') only readout.2, readout.5 and the three "
+                                "sa_k.conv_mask.0.bn run on batch statistics; call frozen_encoder()" % (type(self).__name__, name))
 
     def _frozen_eval(self):
         """frozen_encoder() under a trainable switch: eval() everywhere (folded BatchNorm), except that the readout's two
@@ -632,13 +685,25 @@ class _SaliencyBase(HipModule):
         if what is None:
             return False
         self.eval()
-        if what == "readout":
-            self.readout[2].train()
-            self.readout[5].train()
+        for mod in self._batch_stat_modules().values():
+            mod.train()
         return True
 
     def _tail_with_grad(self, y4):
         r = self.readout
+        if isinstance(y4, tuple) and len(y4) == 5:
+            # trainable("fusion"): the lateral outputs and the masks; autograd.Fusion hands ReadoutHead maps that carry a graph
+            idle = [n for n, m in self._batch_stat_modules().items() if not m.training]
+            if idle:
+                raise MspiError("trainable('fusion'): a forward with grad runs %s on batch statistics, but in eval() mode the "
+                                "no_grad forward folds the running ones; call frozen_encoder() (engine_train.train_one_epoch does)"
+                                % ", ".join(idle))
+            sa, bns = [], []
+            for m in (self.sa_0, self.sa_1, self.sa_2):
+                b, c = m.conv_mask[0], m.conv_mask[2]
+                sa += [b.conv.weight, b.bn.weight, b.bn.bias, c.weight, c.bias]
+                bns.append((b.bn.running_mean, b.bn.running_var, b.bn.num_batches_tracked))
+            y4 = Fusion.apply(*[s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4], *sa, *bns)
         if isinstance(y4, tuple):
             if not (r[2].training and r[5].training):
                 # ReadoutHead normalises with BATCH statistics whatever the modules' mode; in eval() the no_grad forward of the
@@ -646,7 +711,7 @@ class _SaliencyBase(HipModule):
                 raise MspiError("trainable('readout'): a forward with grad runs readout.2 and readout.5 on batch statistics, "
                                 "but they are in eval() mode; call frozen_encoder() (engine_train.train_one_epoch does)")
             bn = [(r[i].running_mean, r[i].running_var, r[i].num_batches_tracked) for i in (2, 5)]
-            maps = [s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4]
+            maps = [s if torch.is_tensor(s) else s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4]
             y = ReadoutHead.apply(*maps, r[0].weight, r[0].bias, r[1].weight, r[1].bias, r[2].weight, r[2].bias, r[4].weight,
                                   r[4].bias, r[5].weight, r[5].bias, bn[0], bn[1])
             return ReadoutTail.apply(y, r[8].weight, r[8].bias, r[10].weight, r[10].bias, r[12].weight, r[12].bias)
@@ -759,7 +824,7 @@ class AudioVisualSaliencyModel(_SaliencyBase):
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
                 masks = self.adapter.run(o1, o0)
-                pm = self._premask(pk, masks)
+                pm = None if features == "laterals" else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             with fk.branch(1):
                 aud = self.audnet.forward_cl(audios.float())
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
@@ -827,7 +892,7 @@ class VisualSaliencyModel(_SaliencyBase):
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
                 masks = self.adapter.run(o1, o0)
-                pm = self._premask(pk, masks)
+                pm = None if features == "laterals" else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
             cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3)
             s3 = self._lateral(pk, 3, [v4])

@@ -1,6 +1,6 @@
-"""Fine-tune the readout (or only its tail) of a checkpoint: the reference's train.py as far as the readout needs it, on the MI355X.
+"""Fine-tune the readout (or only its tail, or the SA gates with it) of a checkpoint: the reference's train.py as far as the readout needs it, on the MI355X.
 
-    python -m mspi_amd.train --trainable readout|readout_tail --weights w.pt --dataset AVAD --split 1 --model x3dl
+    python -m mspi_amd.train --trainable readout|readout_tail|fusion --weights w.pt --dataset AVAD --split 1 --model x3dl
         [--path_data ./AuViDataset] [--log_dir ./training_logs] [--save_ckpt_freq 10] [--gamma 1] [--start_epoch 0]
         [--resolution H W] [--batch 2] [--no_sound] [--workers 8]
 
@@ -8,8 +8,10 @@
 front of them is frozen and runs as in inference, with eval BatchNorm folded into the convolutions.
 --trainable readout: the whole readout Sequential trains, all 16 of its tensors; readout[2] and readout[5] run on batch
 statistics and update their running statistics as upstream's decoder training does (autograd.ReadoutHead).
-Still frozen in both: SA gating, the laterals, the top-down fusion and every encoder.  That is fine-tuning of a released
-checkpoint's readout, not upstream's full training.  As upstream: the training split of
+--trainable fusion: the three SA gates train with the whole readout, 31 tensors; the gates' BatchNorm layers run on batch
+statistics too, and the backward reaches the lateral outputs through the gating and the top-down sums (autograd.Fusion).
+Still frozen in all three: the laterals, the adapter and every encoder (with --trainable readout and readout_tail also the SA
+gating).  That is fine-tuning of a released checkpoint's decoder head, not upstream's full training.  As upstream: the training split of
 avsp_dataloader.AudioVisualDataset, AdamW over the parameters that require grad with weight decay 0, cfg.SOLVER.LR for 60
 epochs then a tenth of it every 60 (lr_by_epoch), a state_dict checkpoint every --save_ckpt_freq epochs and at the end
 (inference.build_model loads them), one JSON line per epoch, printed and appended to <log_dir>/log.txt.  One process, one GPU."""
@@ -21,7 +23,8 @@ import torch
 
 from ._lib import MspiError
 
-TRAINABLE = ("readout_tail", "readout")
+TRAINABLE = ("readout_tail", "readout")           # what trains on a frozen pyramid
+TRAINABLE_STAGES = TRAINABLE + ("fusion",)        # every value --trainable takes
 
 
 def lr_by_epoch(cfg):
@@ -42,15 +45,15 @@ def _single_rank():
 
 
 def check_trainable(value):
-    if value not in TRAINABLE:
-        raise MspiError("--trainable %s: only %s can be trained (the models' backward stops in front of the readout)"
-                        % (value, ", ".join(TRAINABLE)))
+    if value not in TRAINABLE_STAGES:
+        raise MspiError("--trainable %s: only %s can be trained on a frozen pyramid, and %s on frozen laterals (the models' "
+                        "backward stops in front of the laterals)" % (value, ", ".join(TRAINABLE), TRAINABLE_STAGES[-1]))
     return value
 
 
 def build_parser():
     parser = argparse.ArgumentParser(prog="python -m mspi_amd.train", description=__doc__.split("\n")[0])
-    parser.add_argument("--trainable", default="readout_tail", type=str, help="the part of the model that trains: readout_tail or readout")
+    parser.add_argument("--trainable", default="readout_tail", type=str, help="the part of the model that trains: readout_tail, readout or fusion")
     parser.add_argument("--start_epoch", default=0, type=int)
     parser.add_argument("--split", default=1, type=int)
     parser.add_argument("--dataset", default="AVAD", type=str)
@@ -75,7 +78,8 @@ def train(model, data, cfg, device, log_dir, start_epoch=0, save_ckpt_freq=10, g
     from .metrics import SalLoss
     params = [p for p in model.parameters() if p.requires_grad]
     if not params:
-        raise MspiError("train: no parameter requires grad; call model.trainable('readout_tail') or model.trainable('readout') first")
+        raise MspiError("train: no parameter requires grad; call model.trainable('readout_tail'), model.trainable('readout') or "
+                        "model.trainable('fusion') first")
     optimizer = torch.optim.AdamW(params, cfg.SOLVER.LR, weight_decay=0)
     schedule = lr_by_epoch(cfg)
     ckpt_dir = os.path.join(log_dir, "checkpoints")
