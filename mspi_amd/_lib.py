@@ -283,6 +283,18 @@ _TRAIN_SIGNATURES = {
 
 TRAIN_EXPORTS = tuple(_TRAIN_SIGNATURES)
 
+# The ConvNextBlock backward declared in include/mspi_block_train_hip.h (csrc/block_bwd.hip): a third table for the same reason
+_BLOCK_SIGNATURES = {
+    "mspi_gelu_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P]),
+    "mspi_layernorm_bwd_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "mspi_layernorm_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, _P]),
+    "mspi_dwconv_wgrad_supported": (C.c_int, [C.POINTER(DwConvDesc)]),
+    "mspi_dwconv_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(DwConvDesc)]),
+    "mspi_dwconv_wgrad": (C.c_int, [C.POINTER(DwConvDesc), _P, _P, _P, _P, _P, _P]),
+}
+
+BLOCK_EXPORTS = tuple(_BLOCK_SIGNATURES)
+
 _lib = None
 
 
@@ -301,7 +313,7 @@ def load():
     # ROCm-capable device is detected" (seen when build() loaded the library before anything had imported torch).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

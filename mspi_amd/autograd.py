@@ -10,7 +10,10 @@ ReadoutTail's input, so the two together train the whole readout Sequential.
 
 Fusion: the stage in front of that -- the three SA gates (model/model_utils.py:155-170) with their BatchNorm on BATCH
 statistics and the top-down sums of model/model_utils.py:566-567 -- over the four lateral outputs and the adapter's masks.  Its
-outputs are ReadoutHead's maps, whose gradients ReadoutHead computes when they are asked for."""
+outputs are ReadoutHead's maps, whose gradients ReadoutHead computes when they are asked for.
+
+LateralBlock: the ConvNextBlock at the end of each lateral (model/model_utils.py:306-354) over the entry conv's output and the
+block's ten tensors.  Its output is one of Fusion's laterals."""
 import torch
 
 from . import engine as E
@@ -347,3 +350,118 @@ class Fusion(torch.autograd.Function):
             sl = slice(k * mid, (k + 1) * mid)
             grads[5 + 5 * k], grads[5 + 5 * k + 1], grads[5 + 5 * k + 2] = dW[sl], dgam[sl], dbet[sl]
         return tuple(g if g is None or need[i] else None for i, g in enumerate(grads))
+
+
+LN_EPS = 1e-5                            # nn.LayerNorm's default, which ConvNextBlock.norm is built with
+MLP_FUSED_MIN_ROWS = 4096                # from here on the block's LN -> 1x1x1 -> GELU -> 1x1x1 -> +x runs as one launch (E.mlp)
+
+
+def pack_convnext_block(wt, bt, ws, bs, gamma, beta, w1, b1, w2, b2):
+    """The plan of a ConvNextBlock from its ten tensors in their nn layouts: what ConvNextBlock._pack holds and what
+    LateralBlock.forward builds from the live values, so the two cannot drift."""
+    d, hidden = w1.shape[1], w1.shape[0]
+    return {"dt": E.pack_dwconv(wt, bt, None, (1, 1, 1), (3, 0, 0)),
+            "ds": E.pack_dwconv(ws, bs, None, (1, 1, 1), (0, 3, 3)),
+            "ln": (gamma.detach().float().contiguous(), beta.detach().float().contiguous()),
+            "p1": E.pack_conv(w1, b1, act=E.ACT_GELU),
+            "p2": E.pack_conv(w2, b2),
+            # LN -> 1x1x1 -> GELU -> 1x1x1 -> +x in one launch where the fused kernel covers the width (dim 192)
+            "fused": E.pack_mlp(w1.flatten(1), b1, w2.flatten(1), b2) if E.mlp_supported(d, hidden) else None}
+
+
+def convnext_block_forward(x, pk, out=None):
+    """ConvNextBlock.run on the plan pk: (y, a, b) with a = dw_t(x) and b = dw_s(a), which the backward reads."""
+    a = E.dwconv(x, pk["dt"])
+    b = E.dwconv(a, pk["ds"])
+    if pk["fused"] is not None and b.M >= MLP_FUSED_MIN_ROWS:      # below that the two tiled GEMMs (split-K on the small maps) win
+        return E.mlp(b, pk["fused"], res=x, ln=pk["ln"], eps=LN_EPS, out=out, split=(pk["p1"], pk["p2"])), a, b
+    return E.conv(E.conv(E.layernorm(b, *pk["ln"], LN_EPS), pk["p1"]), pk["p2"], res=x, out=out), a, b
+
+
+def _wide_slices(x, dy, over_input):
+    """Weight and bias gradient of a 1x1x1 conv wider than mspi_conv_wgrad_wide_fwd takes, in slices of at most
+    WGRAD_WIDE_MAX_CH channels of x (over_input) or of dy: a slice of the wider tensor as it stands where the kernel accepts
+    its strides, a dense copy where it refuses (Fusion.backward).  Returns (dW [Co,Ci,1,1,1], db [Co])."""
+    wide = x if over_input else dy
+    dWs, dbs = [], []
+    for c0 in range(0, wide.C, WGRAD_WIDE_MAX_CH):
+        c = min(WGRAD_WIDE_MAX_CH, wide.C - c0)
+        xs, ds = (wide.slice(c0, c), dy) if over_input else (x, wide.slice(c0, c))
+        geo = _geometry((1, 1, 1), (0, 0, 0), xs.C, ds.C)
+        if E.conv_wgrad_wide_variant(xs, ds, geo) < 0:
+            dense = E.from_rows(wide.as_rows()[:, c0:c0 + c].contiguous()).reshape(wide.N, wide.T, wide.H, wide.W)
+            xs, ds = (dense, dy) if over_input else (x, dense)
+        dW, db = E.conv_wgrad_wide(xs, ds, geo)
+        dWs.append(dW)
+        dbs.append(db)
+    if len(dWs) == 1:
+        return dWs[0], dbs[0]
+    return (torch.cat(dWs, 1), dbs[0]) if over_input else (torch.cat(dWs, 0), torch.cat(dbs, 0))
+
+
+class LateralBlock(torch.autograd.Function):
+    """y = LateralBlock.apply(x, wt, bt, ws, bs, gamma, beta, w1, b1, w2, b2): the ConvNextBlock of a lateral on x, channels-last
+    fp32 [B,T,h,w,D] on the GPU, D a multiple of 32 -- dwconv_t (7,1,1), dwconv_s (1,7,7), norm.norm, pwconv1 (D -> 4D, GELU) and
+    pwconv2 with weight and bias each, in their nn layouts.  The forward launches what ConvNextBlock.run launches, from packs of
+    the parameters' present values (pack_convnext_block), the switch at MLP_FUSED_MIN_ROWS rows included, so y has the bits of
+    the inference path.  It keeps x, a = dw_t(x) and b = dw_s(a); the backward recomputes n = LN(b) and the 4D-wide
+    z = W1 n + b1, which the fused kernel never stores.  Gradients: the ten tensors, and x only when it requires grad.  No
+    double backward."""
+
+    @staticmethod
+    def forward(ctx, x, wt, bt, ws, bs, gamma, beta, w1, b1, w2, b2):
+        if not x.is_cuda:
+            raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % x.device)
+        if x.dim() != 5 or x.dtype != torch.float32:
+            raise MspiError("LateralBlock: x must be fp32 [B,T,h,w,D] (channels-last), got %s %s" % (x.dtype, tuple(x.shape)))
+        D = x.shape[4]
+        if D % 32:
+            raise MspiError("LateralBlock: D = %d is not a multiple of 32 (D %% 32 != 0)" % D)
+        want = ((D, 1, 7, 1, 1), (D,), (D, 1, 1, 7, 7), (D,), (D,), (D,), (4 * D, D, 1, 1, 1), (4 * D,), (D, 4 * D, 1, 1, 1), (D,))
+        names = ("dwconv_t.weight", "dwconv_t.bias", "dwconv_s.weight", "dwconv_s.bias", "norm.norm.weight", "norm.norm.bias",
+                 "pwconv1.weight", "pwconv1.bias", "pwconv2.weight", "pwconv2.bias")
+        for name, t, shape in zip(names, (wt, bt, ws, bs, gamma, beta, w1, b1, w2, b2), want):
+            if tuple(t.shape) != shape or t.device != x.device:
+                raise MspiError("LateralBlock: %s is %s on %s, a ConvNextBlock of dim %d has %s on %s"
+                                % (name, tuple(t.shape), t.device, D, shape, x.device))
+        x = x.detach().contiguous()
+        with torch.no_grad():
+            pk = pack_convnext_block(wt, bt, ws, bs, gamma, beta, w1, b1, w2, b2)
+            y, a, b = convnext_block_forward(_cl5(x), pk)
+        ctx.save_for_backward(x, a.buf, b.buf, wt, ws, gamma, beta, w1, b1, w2)
+        ctx.packs = (pk["dt"], pk["ds"])
+        return y.buf.view(y.N, y.T, y.H, y.W, y.ld)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        xb, ab, bb, wt, ws, gamma, beta, w1, b1, w2 = ctx.saved_tensors
+        pdt, pds = ctx.packs
+        B, T, h, w, D = xb.shape
+        need = ctx.needs_input_grad
+
+        def cl(buf):
+            return E.CL(buf.view(-1), 0, B, T, h, w, D, D)
+        x, a, b, Gc = cl(xb), cl(ab), cl(bb), cl(G.float().contiguous())
+        gam = gamma.detach().float().contiguous()
+        # the recompute works on activations, so the forward's f16x3 pack serves; the GELU is taken apart from it (z is needed)
+        n = E.layernorm(b, gam, beta.detach().float().contiguous(), LN_EPS)
+        z = E.conv(n, E.pack_conv(w1, b1))                                   # [M, 4D]
+        # the two data-gradient GEMMs on the fp32 MFMA path: their operand is a gradient (ReadoutTail.backward)
+        dg = E.conv(Gc, E.pack_conv(w2.detach().flatten(1).t().contiguous(), None, prec=E.PREC_F32))
+        g, dz = E.gelu_bwd(z, dg, inplace=True)                              # g over z, dz over dg
+        dw2, db2 = _wide_slices(g, Gc, over_input=True)
+        dw1, db1 = _wide_slices(n, dz, over_input=False)
+        dn = E.conv(dz, E.pack_conv(w1.detach().flatten(1).t().contiguous(), None, prec=E.PREC_F32))
+        db_, dgamma, dbeta = E.layernorm_bwd(dn, b, gam, LN_EPS)
+        # padding 3 under kernel 7 is symmetric: the adjoint of a depthwise conv is the same conv on the flipped taps, no bias
+        da = E.dwconv(db_, E.pack_dwconv(ws.detach().flip(2, 3, 4), None, None, (1, 1, 1), (0, 3, 3)))
+        dws, dbs = E.dwconv_wgrad(a, db_, pds)
+        dwt, dbt = E.dwconv_wgrad(x, da, pdt)
+        dx = None
+        if need[0]:
+            dx = E.dwconv(da, E.pack_dwconv(wt.detach().flip(2, 3, 4), None, None, (1, 1, 1), (3, 0, 0)))
+            E.add(dx.buf, Gc.buf, dx.buf)                                                # the residual
+            dx = dx.buf.view(B, T, h, w, D)
+        grads = (dx, dwt, dbt, dws, dbs, dgamma, dbeta, dw1, db1, dw2, db2)
+        return tuple(gr if need[i] else None for i, gr in enumerate(grads))

@@ -158,6 +158,18 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// The ordered add of the slab reducers (readout_train.hip, block_bwd.hip): the sum of S workspace records for one element by 4
+// thread groups: group g adds records g, g + 4, ... in order, then (p0 + p1) + (p2 + p3).  blockDim 256 = 64 elements x 4
+// groups.  Valid in group 0.
+__device__ __forceinline__ float rt_sum_records(const float* __restrict__ p, long stride, int S, bool live, float (*part)[64]) {
+  const int g = threadIdx.x >> 6, e = threadIdx.x & 63;
+  float s = 0.f;
+  if (live)
+    for (int i = g; i < S; i += 4) s += p[(long)i * stride];
+  part[g][e] = s;
+  __syncthreads();
+  return (part[0][e] + part[1][e]) + (part[2][e] + part[3][e]);
+}
 // torch.min: a NaN in either argument is the result (fminf would drop it, and a constant map would score SIM = 1)
 __device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? a + b : fminf(a, b); }
 // torch.max / torch.relu likewise: fmaxf(NaN, 0) is a clean 0, so a poisoned activation would leave a kernel that ends in

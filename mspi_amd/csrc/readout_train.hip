@@ -10,18 +10,6 @@
 
 namespace mspi {
 
-// Sum of S records for one element by 4 thread groups: group g adds records g, g + 4, ... in order, then (p0 + p1) + (p2 + p3).
-// blockDim 256 = 64 elements x 4 groups.  Valid in group 0.
-__device__ __forceinline__ float rt_sum_records(const float* __restrict__ p, long stride, int S, bool live, float (*part)[64]) {
-  const int g = threadIdx.x >> 6, e = threadIdx.x & 63;
-  float s = 0.f;
-  if (live)
-    for (int i = g; i < S; i += 4) s += p[(long)i * stride];
-  part[g][e] = s;
-  __syncthreads();
-  return (part[0][e] + part[1][e]) + (part[2][e] + part[3][e]);
-}
-
 // ------------------------------------------------------------------------------------------------ wide weight gradient
 // A workgroup owns one (32 output channels, 32 input channels) pair, ALL taps of it, and a slice of the output rows.  The
 // rows come as boxes of TR x HR x WR output positions (<= 128 rows) of one sample.  Per box the workgroup stages, once,

@@ -25,7 +25,8 @@ from .packs import (DEFAULT_PREC, SP_ENABLED, PackedConv, PackedDw, PackedMlp, P
 __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedConv", "PackedDw", "conv", "dwconv", "maxpool",
            "layernorm", "attention", "upsample", "upsample_sum", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine", "se_gate",
            "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "conv_wgrad_wide",
-           "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "rowgate_bwd", "upsample_sum_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "rowgate_bwd", "upsample_sum_bwd", "gelu_bwd",
+           "layernorm_bwd", "dwconv_wgrad", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 # ----------------------------------------------------------------------------- conv autotuning
@@ -1283,6 +1284,76 @@ def upsample_sum_bwd(dx, srcs, accumulate=False):
         check(lib.mspi_upsample_sum_bwd(ptrs, lds, ks, J, dx.ptr, dx.ld, dx.N * dx.T, dx.H, dx.W, dx.Cs, 1 if accumulate else 0,
                                         _stream()), "mspi_upsample_sum_bwd")
     return dx
+
+# ----------------------------------------------------------------------------- ConvNextBlock backward (csrc/block_bwd.hip)
+LN_BWD_ROWS = 256               # rows per workgroup record of mspi_layernorm_bwd
+LN_BWD_MAX_CH = 256             # widest row mspi_layernorm_bwd takes
+
+
+def _rows_like(name, what, t, ref):
+    if (t.M, t.C) != (ref.M, ref.C) or not t.dense or t.buf.device != ref.buf.device:
+        raise MspiError("%s: %s must match (%d rows x %d channels, dense, on %s)" % (name, what, ref.M, ref.C, ref.buf.device))
+
+
+def gelu_bwd(z, dg, need_g=True, inplace=False):
+    """Backward of g = GELU(z) (erf form) for the gradient dg: returns (g, dz), CLs like z -- g the forward's activation again
+    (None with need_g=False), dz = dg (Phi(z) + z phi(z)).  inplace=True: g overwrites z and dz overwrites dg."""
+    lib = _lib.load()
+    _need_gpu(z.buf)
+    if not z.dense or z.Cs != z.C:
+        raise MspiError("gelu_bwd: rows must be dense with a channel count that is a multiple of 4 (%d rows x %d)" % (z.M, z.C))
+    _rows_like("gelu_bwd", "dg", dg, z)
+    dev = z.buf.device
+    g = (z if inplace else alloc(z.N, z.T, z.H, z.W, z.C, dev)) if need_g else None
+    dz = dg if inplace else alloc(z.N, z.T, z.H, z.W, z.C, dev)
+    with _Timed("gelu_bwd", 40.0 * z.M * z.C, 4.0 * z.M * z.C * (4 if need_g else 3), "M=%d C=%d" % (z.M, z.C)):
+        check(lib.mspi_gelu_bwd(z.ptr, z.ld, dg.ptr, dg.ld, g.ptr if need_g else None, g.ld if need_g else 0, dz.ptr, dz.ld,
+                                z.M, z.C, _stream()), "mspi_gelu_bwd")
+    return g, dz
+
+
+def layernorm_bwd(dy, x, gamma, eps=1e-5):
+    """Backward of layernorm(x, gamma, beta, eps) over the channels of each row for the output gradient dy; mean and rstd are
+    computed again from x.  Returns (dx, dgamma, dbeta): a CL like x and two fp32 [C]."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    M, Cc = _bn_rows("layernorm_bwd", x)
+    if Cc > LN_BWD_MAX_CH:
+        raise MspiError("layernorm_bwd: rows of %d channels, at most %d" % (Cc, LN_BWD_MAX_CH))
+    _rows_like("layernorm_bwd", "dy", dy, x)
+    dev = x.buf.device
+    gp = _bn_vec("layernorm_bwd", "gamma", gamma, Cc, dev)
+    dx = alloc(x.N, x.T, x.H, x.W, x.C, dev)
+    dgb = torch.empty(2, Cc, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_layernorm_bwd_ws_bytes(M, Cc) // 4, dtype=torch.float32, device=dev)          # stream-ordered
+    with _Timed("layernorm_bwd", 20.0 * M * Cc, 12.0 * M * Cc, "M=%d C=%d" % (M, Cc)):
+        check(lib.mspi_layernorm_bwd(x.ptr, x.ld, dy.ptr, dy.ld, gp, float(eps), dx.ptr, dx.ld, dgb[0].data_ptr(), dgb[1].data_ptr(),
+                                     ws.data_ptr(), M, Cc, _stream()), "mspi_layernorm_bwd")
+    return dx, dgb[0], dgb[1]
+
+
+def dwconv_wgrad(x, dy, pk):
+    """Weight and bias gradient of dwconv(x, pk) for the output gradient dy (in front of any activation); pk gives the layer's
+    geometry only.  Returns (dW, db) in the parameter's own layout, [C,1,kt,kh,kw] and [C]."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    if x.Cs != pk.c_s or dy.Cs != pk.c_s:
+        raise MspiError("dwconv_wgrad: x has %d / dy %d stored channels, the layer %d" % (x.Cs, dy.Cs, pk.c_s))
+    if not x.dense or not dy.dense or (dy.N, dy.T, dy.H, dy.W) != (x.N, x.T, x.H, x.W) or dy.buf.device != x.buf.device:
+        raise MspiError("dwconv_wgrad: dy [%d,%d,%d,%d] must be dense and have the extent of x [%d,%d,%d,%d]"
+                        % (dy.N, dy.T, dy.H, dy.W, x.N, x.T, x.H, x.W))
+    d = _dw_desc(x, pk.k, pk.stride, pk.pad, dy.ld)
+    if not lib.mspi_dwconv_wgrad_supported(C.byref(d)):
+        raise MspiError("dwconv_wgrad: %s" % lib.mspi_last_error().decode("utf-8", "replace"))
+    dev = x.buf.device
+    taps = pk.k[0] * pk.k[1] * pk.k[2]
+    dW = torch.empty(taps, pk.c_s, dtype=torch.float32, device=dev)
+    db = torch.empty(pk.c_s, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_dwconv_wgrad_ws_bytes(C.byref(d)) // 4, dtype=torch.float32, device=dev)      # stream-ordered
+    with _Timed("dwconv_wgrad", 2.0 * x.M * taps * pk.c, 8.0 * x.M * pk.c, "in=%s C=%d k=%s" % ((x.N, x.T, x.H, x.W), pk.c, pk.k)):
+        check(lib.mspi_dwconv_wgrad(C.byref(d), x.ptr, dy.ptr, dW.data_ptr(), db.data_ptr(), ws.data_ptr(), _stream()),
+              "mspi_dwconv_wgrad")
+    return dW[:, :pk.c].t().reshape(pk.c, 1, *pk.k), db[:pk.c]
 
 
 def mean_rows(x, N, R, out):

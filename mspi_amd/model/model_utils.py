@@ -20,7 +20,8 @@ import torch.nn as nn
 
 from .. import engine as E
 from .._lib import MspiError
-from ..autograd import Fusion, ReadoutHead, ReadoutTail, pack_readout_tail, r0_parts, readout_tail_forward
+from ..autograd import (Fusion, LateralBlock, ReadoutHead, ReadoutTail, convnext_block_forward, pack_convnext_block,
+                        pack_readout_tail, r0_parts, readout_tail_forward)
 from ..backbones.convnext import ConvNeXtTinyFeatures
 from ..backbones.resnet import get_resnet18
 from ..module import HipModule, to_cl
@@ -259,22 +260,16 @@ class ConvNextBlock(HipModule):
                 nn.init.trunc_normal_(m.weight, std=0.02)
                 nn.init.constant_(m.bias, 0)
 
+    def tensors(self):
+        """The ten tensors in the order of autograd.LateralBlock's arguments (and of pack_convnext_block's)."""
+        return (self.dwconv_t.weight, self.dwconv_t.bias, self.dwconv_s.weight, self.dwconv_s.bias, self.norm.norm.weight,
+                self.norm.norm.bias, self.pwconv1.weight, self.pwconv1.bias, self.pwconv2.weight, self.pwconv2.bias)
+
     def _pack(self):
-        return {"dt": E.pack_dwconv(self.dwconv_t.weight, self.dwconv_t.bias, None, (1, 1, 1), (3, 0, 0)),
-                "ds": E.pack_dwconv(self.dwconv_s.weight, self.dwconv_s.bias, None, (1, 1, 1), (0, 3, 3)),
-                "ln": (_f(self.norm.norm.weight), _f(self.norm.norm.bias)),
-                "p1": E.pack_conv(self.pwconv1.weight, self.pwconv1.bias, act=E.ACT_GELU),
-                "p2": E.pack_conv(self.pwconv2.weight, self.pwconv2.bias),
-                # LN -> 1x1x1 -> GELU -> 1x1x1 -> +x in one launch where the fused kernel covers the width (dim 192)
-                "fused": E.pack_mlp(self.pwconv1.weight.flatten(1), self.pwconv1.bias, self.pwconv2.weight.flatten(1),
-                                    self.pwconv2.bias) if E.mlp_supported(self.pwconv1.in_channels, self.pwconv1.out_channels) else None}
+        return pack_convnext_block(*self.tensors())
 
     def run(self, x, out=None):
-        pk = self.pk
-        y = E.dwconv(E.dwconv(x, pk["dt"]), pk["ds"])
-        if pk["fused"] is not None and y.M >= 4096:      # below that the two tiled GEMMs (split-K on the small maps) win
-            return E.mlp(y, pk["fused"], res=x, ln=pk["ln"], eps=1e-5, out=out, split=(pk["p1"], pk["p2"]))
-        return E.conv(E.conv(E.layernorm(y, *pk["ln"], 1e-5), pk["p1"]), pk["p2"], res=x, out=out)
+        return convnext_block_forward(x, self.pk, out=out)[0]
 
 
 class StaticSaliencyModelConvNext(HipModule):
@@ -454,17 +449,20 @@ class _SaliencyBase(HipModule):
     def _pack_r0_parts(self, conv):
         return [E.pack_conv(w, b) for w, b in self._r0_parts(conv.weight, conv.bias)]
 
-    def _lateral(self, pk, k, xs, out=None):
+    def _lateral(self, pk, k, xs, out=None, features=False):
+        """latlayer_k: the entry conv(s), then the ConvNextBlock -- left to autograd.LateralBlock when features == "entries"."""
         y = E.conv(xs[0], pk["lat"][k][0])
         if len(xs) == 2:
             y = E.conv(xs[1], pk["lat"][k][1], res=y)
+        if features == "entries":
+            return y
         return getattr(self, "latlayer_%d" % k)[-1].run(y, out=out)
 
-    def _laterals_012(self, pk, v1, v2, v3):
+    def _laterals_012(self, pk, v1, v2, v3, features=False):
         """latlayer_0..2 need only the motion encoder's first three maps: they run while the image branch is still busy.
         MSPI_DECODER_FUSED=0: s0 is produced straight into its channel slice of the readout's 768-channel input."""
         if DECODER_FUSED:
-            return None, self._lateral(pk, 0, [v1]), self._lateral(pk, 1, [v2]), self._lateral(pk, 2, [v3])
+            return (None,) + tuple(self._lateral(pk, k, [v], features=features) for k, v in enumerate((v1, v2, v3)))
         B = v1.N
         cat = E.alloc(B, max(1, v1.T // (self.cfg.MODEL.LATERAL_STRIDE[0] if self.cfg.MODEL.LATERAL_BOOL[0] else 1)),
                       v1.H, v1.W, 4 * 192, v1.buf.device)
@@ -498,8 +496,11 @@ class _SaliencyBase(HipModule):
 
     def _fuse_readout(self, pk, cat, s0, s1, s2, s3, masks, pm, features=False):
         """SA gating, top-down fusion and readout (model/model_utils.py:566-572); features=True stops in front of readout[8]
-        and returns y4 [B,4,h,w,64]; "maps" stops in front of readout[0]; "laterals" in front of the gating (pm is None then)."""
-        if features == "laterals":     # trainable("fusion"): autograd.Fusion takes over from here, then ReadoutHead
+        and returns y4 [B,4,h,w,64]; "maps" stops in front of readout[0]; "laterals" in front of the gating (pm is None then);
+        "entries" likewise, s0..s3 then being the entry convs' outputs (_lateral)."""
+        if features in ("laterals", "entries"):
+            # trainable("fusion"): autograd.Fusion takes over from here, then ReadoutHead; trainable("lateral_blocks"): s0..s3
+            # are the entry convs' outputs, and autograd.LateralBlock comes first
             return s0, s1, s2, s3, masks
         if features != "maps":         # "maps": ReadoutHead packs the live values itself
             self._refresh_head(pk)
@@ -573,9 +574,9 @@ class _SaliencyBase(HipModule):
             self.__dict__.pop("_pk", None)
             return
         with torch.no_grad():
-            if grad_tail != "laterals":    # ... autograd.Fusion for the SA fold, whose premask that forward does not launch
+            if grad_tail not in ("laterals", "entries"):    # ... autograd.Fusion for the SA fold, whose premask that forward does not launch
                 self._refresh_sa(pk)
-            if grad_tail not in ("maps", "laterals"):
+            if grad_tail not in ("maps", "laterals", "entries"):
                 self._refresh_head(pk)
             if not grad_tail:          # ... and ReadoutTail does the same for the tail
                 self._refresh_tail(pk)
@@ -607,7 +608,12 @@ class _SaliencyBase(HipModule):
     TAIL_PARAMS = tuple("readout.%d.%s" % (i, n) for i in (8, 10, 12) for n in ("weight", "bias"))
 
     def trainable(self, what):
-        """trainable("fusion"): the SA gates and the whole readout train -- the 15 tensors of sa_0, sa_1, sa_2 and the readout's
+        """trainable("lateral_blocks"): on top of what "fusion" trains, the ConvNextBlock at the end of each lateral -- the 40
+        tensors of latlayer_k[-1] (dwconv_t, dwconv_s, norm.norm, pwconv1, pwconv2; weight and bias each), 71 in all.  A forward
+        with grad enabled stops each lateral behind its entry conv and hands the four entry outputs to autograd.LateralBlock,
+        then to autograd.Fusion, ReadoutHead and ReadoutTail.  The entry convs latlayer_k[0] / [1], the adapter, the SyncBlock
+        and every encoder stay frozen.
+        trainable("fusion"): the SA gates and the whole readout train -- the 15 tensors of sa_0, sa_1, sa_2 and the readout's
         16 get requires_grad; a forward with grad enabled runs the encoders, the adapter and the laterals as in inference and
         hands the four lateral outputs and the adapter's masks to autograd.Fusion (the three gates with their BatchNorm on BATCH
         statistics, the top-down sums), then to autograd.ReadoutHead and autograd.ReadoutTail.  The laterals, the adapter and
@@ -626,17 +632,20 @@ class _SaliencyBase(HipModule):
                 p.requires_grad_(flag)
             d["_trainable"] = None
             return self
-        if what not in ("readout_tail", "readout", "fusion"):
-            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail', 'readout' and 'fusion' are)"
-                            % (what,))
-        if what in ("readout", "fusion") and not DECODER_FUSED:
+        if what not in ("readout_tail", "readout", "fusion", "lateral_blocks"):
+            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail', 'readout', 'fusion' and "
+                            "'lateral_blocks' are)" % (what,))
+        if what in ("readout", "fusion", "lateral_blocks") and not DECODER_FUSED:
             raise MspiError("trainable(%r) needs the fused decoder path: it is switched off by MSPI_DECODER_FUSED=0" % (what,))
         if d.get("_trainable") is None:
             d["_trainable_saved"] = [(p, p.requires_grad) for p in self.parameters()]
         d["_trainable"] = what
         tail = set(self.TAIL_PARAMS)
+        blocks = tuple("latlayer_%d.%d." % (k, len(getattr(self, "latlayer_%d" % k)) - 1) for k in range(4))
         for name, p in self.named_parameters():
-            if what == "fusion":
+            if what == "lateral_blocks":
+                p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.") + blocks))
+            elif what == "fusion":
                 p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.")))
             else:
                 p.requires_grad_(name.startswith("readout.") if what == "readout" else name in tail)
@@ -646,28 +655,29 @@ class _SaliencyBase(HipModule):
         """{name: module} of the BatchNorm layers that run on batch statistics under the present switch."""
         what = self.__dict__.get("_trainable")
         mods = {}
-        if what in ("readout", "fusion"):
+        if what in ("readout", "fusion", "lateral_blocks"):
             mods.update({"readout.2": self.readout[2], "readout.5": self.readout[5]})
-        if what == "fusion":
+        if what in ("fusion", "lateral_blocks"):        # LayerNorm has no mode: the blocks add nothing
             mods.update({"sa_%d.conv_mask.0.bn" % k: getattr(self, "sa_%d" % k).conv_mask[0].bn for k in range(3)})
         return mods
 
     def _training_tail(self):
         """What _forward stops at when this forward carries a graph: True (the features y4, for autograd.ReadoutTail), "maps"
         (the four pyramid maps, for autograd.ReadoutHead and then ReadoutTail), "laterals" (the lateral outputs and the masks,
-        for autograd.Fusion in front of those two) or False."""
+        for autograd.Fusion in front of those two), "entries" (the laterals' entry-conv outputs and the masks, for
+        autograd.LateralBlock in front of those three) or False."""
         what = self.__dict__.get("_trainable")
         if what is None or not torch.is_grad_enabled():
             return False
-        return {"readout": "maps", "fusion": "laterals"}.get(what, True)
+        return {"readout": "maps", "fusion": "laterals", "lateral_blocks": "entries"}.get(what, True)
 
     def _check_eval(self):
         """The forward's guard.  Under trainable("readout") exactly readout[2] and readout[5] may be in train() (they run on
         batch statistics in autograd.ReadoutHead), under trainable("fusion") also the three conv_mask[0].bn (autograd.Fusion);
-        any other module in train() is refused by name, as the model itself is."""
+        under trainable("lateral_blocks") the same five; any other module in train() is refused by name, as the model itself is."""
         super()._check_eval()
         what = self.__dict__.get("_trainable")
-        if what not in ("readout", "fusion"):
+        if what not in ("readout", "fusion", "lateral_blocks"):
             return
         allowed = {id(m) for m in self._batch_stat_modules().values()}
         for name, mod in self.named_modules():
@@ -675,6 +685,10 @@ class _SaliencyBase(HipModule):
                 if what == "readout":
                     raise MspiError("%s.%s is in train() mode: under trainable('readout') only readout.2 and readout.5 run on "
                                     "batch statistics; call frozen_encoder()" % (type(self).__name__, name))
+                if what == "lateral_blocks":
+                    raise MspiError("%s.%s is in train() mode: under trainable('lateral_blocks') only readout.2, readout.5 and "
+                                    "the three sa_k.conv_mask.0.bn run on batch statistics (the blocks' LayerNorm has no mode); "
+                                    "call frozen_encoder()" % (type(self).__name__, name))
                 raise MspiError("%s.%s is in train() mode: under trainable('fusion') only readout.2, readout.5 and the three "
                                 "sa_k.conv_mask.0.bn run on batch statistics; call frozen_encoder()" % (type(self).__name__, name))
 
@@ -693,17 +707,23 @@ class _SaliencyBase(HipModule):
         r = self.readout
         if isinstance(y4, tuple) and len(y4) == 5:
             # trainable("fusion"): the lateral outputs and the masks; autograd.Fusion hands ReadoutHead maps that carry a graph
+            what = self.__dict__.get("_trainable")
             idle = [n for n, m in self._batch_stat_modules().items() if not m.training]
             if idle:
-                raise MspiError("trainable('fusion'): a forward with grad runs %s on batch statistics, but in eval() mode the "
+                raise MspiError("trainable('%s'): a forward with grad runs %s on batch statistics, but in eval() mode the "
                                 "no_grad forward folds the running ones; call frozen_encoder() (engine_train.train_one_epoch does)"
-                                % ", ".join(idle))
+                                % (what, ", ".join(idle)))
+            if what == "lateral_blocks":
+                # the entry convs' outputs: the four ConvNextBlocks run here, from the live tensors, and carry a graph
+                tensors = [s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4]
+                y4 = [LateralBlock.apply(t, *getattr(self, "latlayer_%d" % k)[-1].tensors()) for k, t in enumerate(tensors[:4])]
+                y4.append(tensors[4])
             sa, bns = [], []
             for m in (self.sa_0, self.sa_1, self.sa_2):
                 b, c = m.conv_mask[0], m.conv_mask[2]
                 sa += [b.conv.weight, b.bn.weight, b.bn.bias, c.weight, c.bias]
                 bns.append((b.bn.running_mean, b.bn.running_var, b.bn.num_batches_tracked))
-            y4 = Fusion.apply(*[s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4], *sa, *bns)
+            y4 = Fusion.apply(*[s if torch.is_tensor(s) else s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4], *sa, *bns)
         if isinstance(y4, tuple):
             if not (r[2].training and r[5].training):
                 # ReadoutHead normalises with BATCH statistics whatever the modules' mode; in eval() the no_grad forward of the
@@ -824,16 +844,16 @@ class AudioVisualSaliencyModel(_SaliencyBase):
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
                 masks = self.adapter.run(o1, o0)
-                pm = None if features == "laterals" else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
+                pm = None if features in ("laterals", "entries") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             with fk.branch(1):
                 aud = self.audnet.forward_cl(audios.float())
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
-            cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3)
+            cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3, features)
             fk.join(1)
-            s3, loss = self._sync_and_lateral3(pk, v4, aud, fk)
+            s3, loss = self._sync_and_lateral3(pk, v4, aud, fk, features)
         return self._fuse_readout(pk, cat, s0, s1, s2, s3, masks, pm, features), loss
 
-    def _sync_and_lateral3(self, pk, v4, aud, fk):
+    def _sync_and_lateral3(self, pk, v4, aud, fk, features=False):
         B, dev = v4.N, v4.buf.device
         x = self.aud_vis_sync_block.run(v4, aud)
         Rv = v4.T * v4.H * v4.W
@@ -851,7 +871,7 @@ class AudioVisualSaliencyModel(_SaliencyBase):
             loss = torch.empty(1, dtype=torch.float32, device=dev)
             E.neg_cosine(vis_pred, aud_emb, loss, 0.5, False)
             E.neg_cosine(aud_pred, vis_emb, loss, 0.5, True)
-        return self._lateral(pk, 3, [v4, vis_fea]), loss[0]
+        return self._lateral(pk, 3, [v4, vis_fea], features=features), loss[0]
 
 
 class VisualSaliencyModel(_SaliencyBase):
@@ -892,8 +912,8 @@ class VisualSaliencyModel(_SaliencyBase):
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
                 masks = self.adapter.run(o1, o0)
-                pm = None if features == "laterals" else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
+                pm = None if features in ("laterals", "entries") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
-            cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3)
-            s3 = self._lateral(pk, 3, [v4])
+            cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3, features)
+            s3 = self._lateral(pk, 3, [v4], features=features)
         return self._fuse_readout(pk, cat, s0, s1, s2, s3, masks, pm, features)
