@@ -295,6 +295,16 @@ _BLOCK_SIGNATURES = {
 
 BLOCK_EXPORTS = tuple(_BLOCK_SIGNATURES)
 
+# The entry convs' weight gradient declared in include/mspi_entry_train_hip.h (csrc/entry_bwd.hip): a fourth table, likewise
+_ENTRY_SIGNATURES = {
+    "mspi_conv_wgrad_entry_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "mspi_conv_wgrad_entry_ws_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "mspi_conv_wgrad_entry_variant": (C.c_int, [C.POINTER(ConvDesc), _P, _P]),
+    "mspi_conv_wgrad_entry": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
+}
+
+ENTRY_EXPORTS = tuple(_ENTRY_SIGNATURES)
+
 _lib = None
 
 
@@ -313,7 +323,8 @@ def load():
     # ROCm-capable device is detected" (seen when build() loaded the library before anything had imported torch).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
+            list(_ENTRY_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

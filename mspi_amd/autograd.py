@@ -13,7 +13,11 @@ statistics and the top-down sums of model/model_utils.py:566-567 -- over the fou
 outputs are ReadoutHead's maps, whose gradients ReadoutHead computes when they are asked for.
 
 LateralBlock: the ConvNextBlock at the end of each lateral (model/model_utils.py:306-354) over the entry conv's output and the
-block's ten tensors.  Its output is one of Fusion's laterals."""
+block's ten tensors.  Its output is one of Fusion's laterals.
+
+LateralEntry: the entry conv(s) in front of that block -- latlayer_k[0], 1x1x1 C_k -> 192 with bias, and where present
+latlayer_k[1], (s,1,1) / stride (s,1,1) 192 -> 192 without bias, run composed as one conv (compose_lateral) -- over the
+encoder map(s).  Its output is LateralBlock's input, whose gradient LateralBlock computes when it is asked for."""
 import torch
 
 from . import engine as E
@@ -213,10 +217,10 @@ SA_FACTORS = (4, 2, 1)                   # sa_0, sa_1, sa_2 up-sample their prem
 WGRAD_WIDE_MAX_CH = 192                  # widest stored channel count mspi_conv_wgrad_wide_fwd takes
 
 
-def _geometry(k, pad, cin, cout):
-    """What conv_wgrad_wide reads of a pack (the layer's geometry), without packing any weights."""
+def _geometry(k, pad, cin, cout, stride=(1, 1, 1)):
+    """What conv_wgrad_wide / conv_wgrad_entry read of a pack (the layer's geometry), without packing any weights."""
     p = E.PackedConv()
-    p.k, p.stride, p.pad, p.cin, p.cin_s, p.cout, p.cout_s = k, (1, 1, 1), pad, cin, cin, cout, cout
+    p.k, p.stride, p.pad, p.cin, p.cin_s, p.cout, p.cout_s = k, stride, pad, cin, cin, cout, cout
     return p
 
 
@@ -464,4 +468,132 @@ class LateralBlock(torch.autograd.Function):
             E.add(dx.buf, Gc.buf, dx.buf)                                                # the residual
             dx = dx.buf.view(B, T, h, w, D)
         grads = (dx, dwt, dbt, dws, dbs, dgamma, dbeta, dw1, db1, dw2, db2)
+        return tuple(gr if need[i] else None for i, gr in enumerate(grads))
+
+
+def compose_lateral(w0, b0, w1):
+    """(s,1,1)/s conv after a 1x1x1 conv, no nonlinearity between: one conv with
+    W[co,ci,tap] = sum_m W1[co,m,tap] W0[m,ci],  b[co] = sum_{tap,m} W1[co,m,tap] b0[m], composed in fp64."""
+    w0 = w0.detach().double().flatten(1)                         # [mid, cin]
+    w1 = w1.detach().double()[:, :, :, 0, 0]                      # [co, mid, s]
+    w = torch.einsum("omt,mi->oit", w1, w0)[:, :, :, None, None]  # [co, cin, s, 1, 1]
+    b = torch.einsum("omt,m->o", w1, b0.detach().double())
+    return w.float(), b.float()
+
+
+def pack_lateral_entry(w0, b0, w1, stride, split=None):
+    """The pack(s) of a lateral's entry conv(s) from the tensors in their nn layouts (w1 None: no second conv): what
+    _SaliencyBase._pack_lateral holds and what LateralEntry.forward builds from the live values, so the two cannot drift.
+    split = C4: the input arrives as two tensors, so the K range is cut in two, the bias on the first part."""
+    if w1 is not None:
+        w, b = compose_lateral(w0, b0, w1)
+    else:
+        w, b, stride = w0.detach().float(), b0.detach().float(), (1, 1, 1)
+    if split is None:
+        return (E.pack_conv(w, b, None, stride, (0, 0, 0)),)
+    return (E.pack_conv(w[:, :split].contiguous(), b, None, stride, (0, 0, 0)),
+            E.pack_conv(w[:, split:].contiguous(), None, None, stride, (0, 0, 0)))
+
+
+def _cl_view(name, t):
+    """A CL over the tensor t [B,T,h,w,C] as it lies in memory: frames, lines and positions nested (a channel slice of a wider
+    buffer keeps its row stride), any sample stride (a token view into a slab)."""
+    if t.dim() != 5 or t.dtype != torch.float32:
+        raise MspiError("LateralEntry: %s must be fp32 [B,T,h,w,C] (channels-last), got %s %s" % (name, t.dtype, tuple(t.shape)))
+    B, T, h, w, c = t.shape
+    sN, sT, sH, sW, sC = t.stride()
+    if sC != 1 or sW % 4 or sW < c or sH != w * sW or sT != h * sH or sN % 4 or t.data_ptr() % 16:
+        t = t.contiguous()
+        sN, sW = T * h * w * c, c
+    return E.CL(t, 0, B, T, h, w, c, sW, sN)
+
+
+class LateralEntry(torch.autograd.Function):
+    """y = LateralEntry.apply(x, x2, w0, b0, w1): the entry conv(s) of a lateral on x, channels-last fp32 [B,T,h,w,C] on the GPU
+    (a channel slice of a wider buffer or a token view into a slab is read where it lies), and, x2 not None, on the concat
+    [x | x2] without materialising it.  w0 [192,C(+C2),1,1,1] and b0 of latlayer_k[0]; w1 [192,192,s,1,1] of latlayer_k[1] or
+    None, s in {1, 2, 4}.  The forward composes the two convs in fp64 from the live tensors, packs as _SaliencyBase._pack_lateral
+    does and launches what _SaliencyBase._lateral launches, so y [B,T//s,h,w,192] has the bits of the inference path.  The
+    backward takes dWc, dbc of the COMPOSED conv from mspi_conv_wgrad_entry and applies the chain rule through the composition
+        dW1[co,m,t] = sum_ci dWc[co,ci,t] W0[m,ci] + dbc[co] b0[m]
+        dW0[m,ci]   = sum_{co,t} W1[co,m,t] dWc[co,ci,t],   db0[m] = sum_{co,t} W1[co,m,t] dbc[co]
+    as two GEMMs on the fp32 MFMA path (E.conv at PREC_F32), the bias terms riding as one more column / row; without w1,
+    dW0 = dWc and db0 = dbc.  Gradients: w0, b0, w1.  x and x2 get NONE: the encoders and the SyncBlock stay frozen, and no
+    kernel here computes the entry convs' data gradient.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, x2, w0, b0, w1):
+        if not x.is_cuda or (x2 is not None and x2.device != x.device):
+            raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % x.device)
+        xc = _cl_view("x", x.detach())
+        xc2 = None if x2 is None else _cl_view("x2", x2.detach())
+        cin = xc.C + (xc2.C if xc2 is not None else 0)
+        mid = w0.shape[0]
+        if w0.dim() != 5 or tuple(w0.shape[1:]) != (cin, 1, 1, 1) or tuple(b0.shape) != (mid,) or w0.device != x.device:
+            raise MspiError("LateralEntry: latlayer[0] is %s / %s on %s, the input has %d channels on %s"
+                            % (tuple(w0.shape), tuple(b0.shape), w0.device, cin, x.device))
+        s = 1
+        if w1 is not None:
+            s = w1.shape[2] if w1.dim() == 5 else 0
+            if w1.dim() != 5 or tuple(w1.shape) != (w1.shape[0], mid, s, 1, 1) or s not in (1, 2, 4) or w1.device != x.device:
+                raise MspiError("LateralEntry: latlayer[1] is %s, not an (s,1,1) conv over %d channels with s in {1, 2, 4}"
+                                % (tuple(w1.shape), mid))
+        if xc2 is not None and (xc2.N, xc2.T, xc2.H, xc2.W) != (xc.N, xc.T, xc.H, xc.W):
+            raise MspiError("LateralEntry: x2 %s does not have the extent of x %s" % (tuple(x2.shape), tuple(x.shape)))
+        if xc.T < s:
+            raise MspiError("LateralEntry: %d frames under a temporal kernel of %d" % (xc.T, s))
+        with torch.no_grad():
+            pks = pack_lateral_entry(w0, b0, w1, (s, 1, 1), None if xc2 is None else xc.C)
+            y = E.conv(xc, pks[0])
+            if xc2 is not None:
+                y = E.conv(xc2, pks[1], res=y)
+        views = [xc] + ([] if xc2 is None else [xc2])
+        ctx.save_for_backward(*[v.buf for v in views], w0, b0, *([] if w1 is None else [w1]))
+        ctx.dims = [(v.N, v.T, v.H, v.W, v.C, v.ld, v.sN) for v in views]
+        ctx.has1 = w1 is not None
+        ctx.geoms = [_geometry((s, 1, 1), (0, 0, 0), p.cin, p.cout_s, (s, 1, 1)) for p in pks]
+        return y.buf.view(y.N, y.T, y.H, y.W, y.ld)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        saved = list(ctx.saved_tensors)
+        views = [E.CL(saved.pop(0), 0, *dims) for dims in ctx.dims]
+        xc, xc2, has2, has1 = views[0], views[-1], len(views) == 2, ctx.has1
+        w0, b0 = saved[0], saved[1]
+        w1 = saved[2] if has1 else None
+        need = ctx.needs_input_grad
+        if not any(need[2:]):
+            return None, None, None, None, None
+        Gc = _cl5(G.float().contiguous())
+        # raw [Co][s][Ci] blocks of the composed conv's gradient, the two inputs' column blocks side by side; dbc once
+        dWc, dbc = E.conv_wgrad_entry(xc, Gc, ctx.geoms[0])
+        if has2:
+            dWc = torch.cat([dWc, E.conv_wgrad_entry(xc2, Gc, ctx.geoms[1])[0]], dim=1)
+        if not has1:
+            return None, None, (dWc.contiguous() if need[2] else None), (dbc if need[3] else None), None
+        Co, Ci, s = dWc.shape[:3]
+        mid = w0.shape[0]
+        dev = dWc.device
+        rows = dWc[:, :, :, 0, 0].permute(0, 2, 1)                                    # [Co, s, Ci]
+        dw0 = db0 = dw1 = None
+        if need[4]:
+            # rows (co, t), K = Ci and one more column for the bias term (padded to four), N = mid
+            a = torch.zeros(Co * s, Ci + 4, dtype=torch.float32, device=dev)
+            a[:, :Ci] = rows.reshape(Co * s, Ci)
+            a[:, Ci] = dbc.repeat_interleave(s)
+            wb = torch.zeros(mid, Ci + 4, dtype=torch.float32, device=dev)
+            wb[:, :Ci] = w0.detach().float().flatten(1)
+            wb[:, Ci] = b0.detach().float()
+            out = E.conv(E.from_rows(a), E.pack_conv(wb, None, prec=E.PREC_F32))      # [Co s, mid]
+            dw1 = out.as_rows(mid).reshape(Co, s, mid).permute(0, 2, 1)[:, :, :, None, None]
+        if need[2] or need[3]:
+            # rows ci and one more for db0, K = (co, t), N = mid
+            a = torch.empty(Ci + 1, Co * s, dtype=torch.float32, device=dev)
+            a[:Ci] = rows.permute(2, 0, 1).reshape(Ci, Co * s)
+            a[Ci] = dbc.repeat_interleave(s)
+            wt = w1.detach().float()[:, :, :, 0, 0].permute(1, 0, 2).reshape(mid, Co * s).contiguous()
+            out = E.conv(E.from_rows(a), E.pack_conv(wt, None, prec=E.PREC_F32)).as_rows(mid)      # [Ci + 1, mid]
+            dw0, db0 = out[:Ci].t()[:, :, None, None, None], out[Ci]
+        grads = (None, None, dw0, db0, dw1)
         return tuple(gr if need[i] else None for i, gr in enumerate(grads))

@@ -26,7 +26,7 @@ __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedC
            "layernorm", "attention", "upsample", "upsample_sum", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine", "se_gate",
            "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "conv_wgrad_wide",
            "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "rowgate_bwd", "upsample_sum_bwd", "gelu_bwd",
-           "layernorm_bwd", "dwconv_wgrad", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "layernorm_bwd", "dwconv_wgrad", "conv_wgrad_entry", "conv_wgrad_entry_variant", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 # ----------------------------------------------------------------------------- conv autotuning
@@ -1354,6 +1354,43 @@ def dwconv_wgrad(x, dy, pk):
         check(lib.mspi_dwconv_wgrad(C.byref(d), x.ptr, dy.ptr, dW.data_ptr(), db.data_ptr(), ws.data_ptr(), _stream()),
               "mspi_dwconv_wgrad")
     return dW[:, :pk.c].t().reshape(pk.c, 1, *pk.k), db[:pk.c]
+
+
+# ----------------------------------------------------------------------------- lateral entry convs (csrc/entry_bwd.hip)
+WGRAD_ENTRY_SLICES = (64, 256, 512)     # rows per slice: the codes mspi_conv_wgrad_entry_variant answers
+WGRAD_ENTRY_ROWS = (1024, 32768)        # output rows from which the second and the third are taken
+WGRAD_ENTRY_MAX_CIN = 2560              # widest stored input mspi_conv_wgrad_entry takes
+
+
+def conv_wgrad_entry_variant(x, dy, pk):
+    """The instantiation conv_wgrad_entry(x, dy, pk) launches (rows per slice), -1 where it refuses; host only."""
+    return _lib.load().mspi_conv_wgrad_entry_variant(C.byref(_wgrad_desc(x, dy, pk)), x.ptr, dy.ptr)
+
+
+def conv_wgrad_entry(x, dy, pk):
+    """conv_wgrad for the laterals' entry convs: kernel (s,1,1) == stride, s in {1, 2, 4}, no padding, stored Cout a multiple of
+    32 up to 192, stored Cin any multiple of 4 up to 2560; x may be a channel slice of a wider buffer or a token view into a
+    slab (its own sample stride).  pk gives the layer's geometry only.  Returns (dW [Co,Ci,s,1,1], db [Co])."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    if x.Cs != pk.cin_s or dy.Cs != pk.cout_s:
+        raise MspiError("conv_wgrad_entry: x has %d / dy %d stored channels, the layer %d -> %d" % (x.Cs, dy.Cs, pk.cin_s, pk.cout_s))
+    d = _wgrad_desc(x, dy, pk)
+    if not dy.dense or dy.M != x.N * d.To * d.Ho * d.Wo or dy.buf.device != x.buf.device:
+        raise MspiError("conv_wgrad_entry: dy has %d rows, the layer's output %d (or dy is not dense)"
+                        % (dy.M, x.N * d.To * d.Ho * d.Wo))
+    if lib.mspi_conv_wgrad_entry_variant(C.byref(d), x.ptr, dy.ptr) < 0:
+        raise MspiError("conv_wgrad_entry: %s" % lib.mspi_last_error().decode("utf-8", "replace"))
+    dev = x.buf.device
+    s = pk.k[0]
+    dW = torch.empty(pk.cout_s, s, 1, 1, pk.cin_s, dtype=torch.float32, device=dev)
+    db = torch.empty(pk.cout_s, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_conv_wgrad_entry_ws_bytes(C.byref(d)) // 4, dtype=torch.float32, device=dev)   # stream-ordered
+    with _Timed("conv_wgrad_entry", 2.0 * dy.M * s * pk.cin * pk.cout, 4.0 * dy.M * (s * pk.cin + pk.cout),
+                "M=%d K=%d(%dx%d) N=%d" % (dy.M, s * pk.cin, s, pk.cin, pk.cout)):
+        check(lib.mspi_conv_wgrad_entry(C.byref(d), x.ptr, dy.ptr, dW.data_ptr(), db.data_ptr(), ws.data_ptr(), _stream()),
+              "mspi_conv_wgrad_entry")
+    return dW[:pk.cout, :, :, :, :pk.cin].permute(0, 4, 1, 2, 3), db[:pk.cout]
 
 
 def mean_rows(x, N, R, out):

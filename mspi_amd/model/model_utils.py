@@ -20,8 +20,8 @@ import torch.nn as nn
 
 from .. import engine as E
 from .._lib import MspiError
-from ..autograd import (Fusion, LateralBlock, ReadoutHead, ReadoutTail, convnext_block_forward, pack_convnext_block,
-                        pack_readout_tail, r0_parts, readout_tail_forward)
+from ..autograd import (Fusion, LateralBlock, LateralEntry, ReadoutHead, ReadoutTail, compose_lateral, convnext_block_forward,
+                        pack_convnext_block, pack_lateral_entry, pack_readout_tail, r0_parts, readout_tail_forward)
 from ..backbones.convnext import ConvNeXtTinyFeatures
 from ..backbones.resnet import get_resnet18
 from ..module import HipModule, to_cl
@@ -363,13 +363,8 @@ DECODER_FUSED = os.environ.get("MSPI_DECODER_FUSED", "1") != "0"   # A/B switch:
 
 
 def _compose_lateral(c0, c1):
-    """(s,1,1)/s conv after a 1x1x1 conv, no nonlinearity between: one conv with
-    W[co,ci,tap] = sum_m W1[co,m,tap] W0[m,ci],  b[co] = sum_{tap,m} W1[co,m,tap] b0[m]."""
-    w0 = c0.weight.detach().double().flatten(1)                 # [mid, cin]
-    w1 = c1.weight.detach().double()[:, :, :, 0, 0]              # [co, mid, s]
-    w = torch.einsum("omt,mi->oit", w1, w0)[:, :, :, None, None]  # [co, cin, s, 1, 1]
-    b = torch.einsum("omt,m->o", w1, c0.bias.detach().double())
-    return w.float(), b.float()
+    """The composed conv of two entry modules (autograd.compose_lateral)."""
+    return compose_lateral(c0.weight, c0.bias, c1.weight)
 
 
 class _SaliencyBase(HipModule):
@@ -413,14 +408,8 @@ class _SaliencyBase(HipModule):
         (v4 | vis_sync, the torch.cat of model/model_utils.py:559), so the K range is cut in two."""
         seq = getattr(self, "latlayer_%d" % k)
         if len(seq) == 3:
-            w, b = _compose_lateral(seq[0], seq[1])
-            stride = seq[1].stride
-        else:
-            w, b, stride = seq[0].weight.detach().float(), seq[0].bias.detach().float(), (1, 1, 1)
-        if split is None:
-            return (E.pack_conv(w, b, None, stride, (0, 0, 0)),)
-        return (E.pack_conv(w[:, :split].contiguous(), b, None, stride, (0, 0, 0)),
-                E.pack_conv(w[:, split:].contiguous(), None, None, stride, (0, 0, 0)))
+            return pack_lateral_entry(seq[0].weight, seq[0].bias, seq[1].weight, tuple(seq[1].stride), split)
+        return pack_lateral_entry(seq[0].weight, seq[0].bias, None, (1, 1, 1), split)
 
     def _pack_decoder(self, split=None):
         r = self.readout
@@ -450,7 +439,11 @@ class _SaliencyBase(HipModule):
         return [E.pack_conv(w, b) for w, b in self._r0_parts(conv.weight, conv.bias)]
 
     def _lateral(self, pk, k, xs, out=None, features=False):
-        """latlayer_k: the entry conv(s), then the ConvNextBlock -- left to autograd.LateralBlock when features == "entries"."""
+        """latlayer_k: the entry conv(s), then the ConvNextBlock -- left to autograd.LateralBlock when features == "entries";
+        features == "inputs" stops in front of the entry conv(s) and returns the encoder map(s) for autograd.LateralEntry, split
+        planes joined into fp32 rows."""
+        if features == "inputs":
+            return [E.join_planes(x) if isinstance(x, E.SP) else x for x in xs]
         y = E.conv(xs[0], pk["lat"][k][0])
         if len(xs) == 2:
             y = E.conv(xs[1], pk["lat"][k][1], res=y)
@@ -497,10 +490,12 @@ class _SaliencyBase(HipModule):
     def _fuse_readout(self, pk, cat, s0, s1, s2, s3, masks, pm, features=False):
         """SA gating, top-down fusion and readout (model/model_utils.py:566-572); features=True stops in front of readout[8]
         and returns y4 [B,4,h,w,64]; "maps" stops in front of readout[0]; "laterals" in front of the gating (pm is None then);
-        "entries" likewise, s0..s3 then being the entry convs' outputs (_lateral)."""
-        if features in ("laterals", "entries"):
+        "entries" likewise, s0..s3 then being the entry convs' outputs (_lateral); "inputs" likewise, s0..s3 being the lists of
+        encoder maps the entry convs read."""
+        if features in ("laterals", "entries", "inputs"):
             # trainable("fusion"): autograd.Fusion takes over from here, then ReadoutHead; trainable("lateral_blocks"): s0..s3
-            # are the entry convs' outputs, and autograd.LateralBlock comes first
+            # are the entry convs' outputs, and autograd.LateralBlock comes first; trainable("lateral_entries"): the entry
+            # convs' inputs, and autograd.LateralEntry comes before that
             return s0, s1, s2, s3, masks
         if features != "maps":         # "maps": ReadoutHead packs the live values itself
             self._refresh_head(pk)
@@ -574,9 +569,9 @@ class _SaliencyBase(HipModule):
             self.__dict__.pop("_pk", None)
             return
         with torch.no_grad():
-            if grad_tail not in ("laterals", "entries"):    # ... autograd.Fusion for the SA fold, whose premask that forward does not launch
+            if grad_tail not in ("laterals", "entries", "inputs"):    # ... autograd.Fusion for the SA fold, whose premask that forward does not launch
                 self._refresh_sa(pk)
-            if grad_tail not in ("maps", "laterals", "entries"):
+            if grad_tail not in ("maps", "laterals", "entries", "inputs"):
                 self._refresh_head(pk)
             if not grad_tail:          # ... and ReadoutTail does the same for the tail
                 self._refresh_tail(pk)
@@ -608,7 +603,13 @@ class _SaliencyBase(HipModule):
     TAIL_PARAMS = tuple("readout.%d.%s" % (i, n) for i in (8, 10, 12) for n in ("weight", "bias"))
 
     def trainable(self, what):
-        """trainable("lateral_blocks"): on top of what "fusion" trains, the ConvNextBlock at the end of each lateral -- the 40
+        """trainable("lateral_entries"): on top of what "lateral_blocks" trains, the laterals' entry convs -- latlayer_k[0]
+        (1x1x1, weight and bias) and, where cfg.MODEL.LATERAL_BOOL[k] is set, latlayer_k[1] ((s,1,1) / stride (s,1,1), weight):
+        12 more tensors with the all-composed encoders (83 in all), 10 with s3d (81), 8 with slowfast (79).  A forward with grad
+        enabled stops each lateral IN FRONT of its entry conv(s) and hands the encoder maps to autograd.LateralEntry, then to
+        autograd.LateralBlock, Fusion, ReadoutHead and ReadoutTail; the same five BatchNorm layers run on batch statistics.  The
+        entry convs' inputs get no gradient: the adapter, the masks' gradient, the SyncBlock and every encoder stay frozen.
+        trainable("lateral_blocks"): on top of what "fusion" trains, the ConvNextBlock at the end of each lateral -- the 40
         tensors of latlayer_k[-1] (dwconv_t, dwconv_s, norm.norm, pwconv1, pwconv2; weight and bias each), 71 in all.  A forward
         with grad enabled stops each lateral behind its entry conv and hands the four entry outputs to autograd.LateralBlock,
         then to autograd.Fusion, ReadoutHead and ReadoutTail.  The entry convs latlayer_k[0] / [1], the adapter, the SyncBlock
@@ -632,10 +633,10 @@ class _SaliencyBase(HipModule):
                 p.requires_grad_(flag)
             d["_trainable"] = None
             return self
-        if what not in ("readout_tail", "readout", "fusion", "lateral_blocks"):
-            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail', 'readout', 'fusion' and "
-                            "'lateral_blocks' are)" % (what,))
-        if what in ("readout", "fusion", "lateral_blocks") and not DECODER_FUSED:
+        if what not in ("readout_tail", "readout", "fusion", "lateral_blocks", "lateral_entries"):
+            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail', 'readout', 'fusion', "
+                            "'lateral_blocks' and 'lateral_entries' are)" % (what,))
+        if what in ("readout", "fusion", "lateral_blocks", "lateral_entries") and not DECODER_FUSED:
             raise MspiError("trainable(%r) needs the fused decoder path: it is switched off by MSPI_DECODER_FUSED=0" % (what,))
         if d.get("_trainable") is None:
             d["_trainable_saved"] = [(p, p.requires_grad) for p in self.parameters()]
@@ -643,7 +644,9 @@ class _SaliencyBase(HipModule):
         tail = set(self.TAIL_PARAMS)
         blocks = tuple("latlayer_%d.%d." % (k, len(getattr(self, "latlayer_%d" % k)) - 1) for k in range(4))
         for name, p in self.named_parameters():
-            if what == "lateral_blocks":
+            if what == "lateral_entries":      # every tensor of the four laterals
+                p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.", "latlayer_")))
+            elif what == "lateral_blocks":
                 p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.") + blocks))
             elif what == "fusion":
                 p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.")))
@@ -655,9 +658,9 @@ class _SaliencyBase(HipModule):
         """{name: module} of the BatchNorm layers that run on batch statistics under the present switch."""
         what = self.__dict__.get("_trainable")
         mods = {}
-        if what in ("readout", "fusion", "lateral_blocks"):
+        if what in ("readout", "fusion", "lateral_blocks", "lateral_entries"):
             mods.update({"readout.2": self.readout[2], "readout.5": self.readout[5]})
-        if what in ("fusion", "lateral_blocks"):        # LayerNorm has no mode: the blocks add nothing
+        if what in ("fusion", "lateral_blocks", "lateral_entries"):        # LayerNorm has no mode, convs neither: the laterals add nothing
             mods.update({"sa_%d.conv_mask.0.bn" % k: getattr(self, "sa_%d" % k).conv_mask[0].bn for k in range(3)})
         return mods
 
@@ -665,19 +668,20 @@ class _SaliencyBase(HipModule):
         """What _forward stops at when this forward carries a graph: True (the features y4, for autograd.ReadoutTail), "maps"
         (the four pyramid maps, for autograd.ReadoutHead and then ReadoutTail), "laterals" (the lateral outputs and the masks,
         for autograd.Fusion in front of those two), "entries" (the laterals' entry-conv outputs and the masks, for
-        autograd.LateralBlock in front of those three) or False."""
+        autograd.LateralBlock in front of those three), "inputs" (the encoder maps the entry convs read and the masks, for
+        autograd.LateralEntry in front of those four) or False."""
         what = self.__dict__.get("_trainable")
         if what is None or not torch.is_grad_enabled():
             return False
-        return {"readout": "maps", "fusion": "laterals", "lateral_blocks": "entries"}.get(what, True)
+        return {"readout": "maps", "fusion": "laterals", "lateral_blocks": "entries", "lateral_entries": "inputs"}.get(what, True)
 
     def _check_eval(self):
         """The forward's guard.  Under trainable("readout") exactly readout[2] and readout[5] may be in train() (they run on
         batch statistics in autograd.ReadoutHead), under trainable("fusion") also the three conv_mask[0].bn (autograd.Fusion);
-        under trainable("lateral_blocks") the same five; any other module in train() is refused by name, as the model itself is."""
+        under trainable("lateral_blocks") and trainable("lateral_entries") the same five; any other module in train() is refused by name, as the model itself is."""
         super()._check_eval()
         what = self.__dict__.get("_trainable")
-        if what not in ("readout", "fusion", "lateral_blocks"):
+        if what not in ("readout", "fusion", "lateral_blocks", "lateral_entries"):
             return
         allowed = {id(m) for m in self._batch_stat_modules().values()}
         for name, mod in self.named_modules():
@@ -689,6 +693,10 @@ class _SaliencyBase(HipModule):
                     raise MspiError("%s.%s is in train() mode: under trainable('lateral_blocks') only readout.2, readout.5 and "
                                     "the three sa_k.conv_mask.0.bn run on batch statistics (the blocks' LayerNorm has no mode); "
                                     "call frozen_encoder()" % (type(self).__name__, name))
+                if what == "lateral_entries":
+                    raise MspiError("%s.%s is in train() mode: under trainable('lateral_entries') only readout.2, readout.5 and "
+                                    "the three sa_k.conv_mask.0.bn run on batch statistics (neither the entry convs nor the "
+                                    "blocks' LayerNorm have a mode); call frozen_encoder()" % (type(self).__name__, name))
                 raise MspiError("%s.%s is in train() mode: under trainable('fusion') only readout.2, readout.5 and the three "
                                 "sa_k.conv_mask.0.bn run on batch statistics; call frozen_encoder()" % (type(self).__name__, name))
 
@@ -713,7 +721,19 @@ class _SaliencyBase(HipModule):
                 raise MspiError("trainable('%s'): a forward with grad runs %s on batch statistics, but in eval() mode the "
                                 "no_grad forward folds the running ones; call frozen_encoder() (engine_train.train_one_epoch does)"
                                 % (what, ", ".join(idle)))
-            if what == "lateral_blocks":
+            if what == "lateral_entries":
+                # the encoder maps: the entry convs run here, from the live tensors, and their outputs carry a graph
+                entries = []
+                for k, xs in enumerate(y4[:4]):
+                    seq = getattr(self, "latlayer_%d" % k)
+                    ts = [x.buf.as_strided((x.N, x.T, x.H, x.W, x.C), (x.sN, x.H * x.W * x.ld, x.W * x.ld, x.ld, 1),
+                                           x.buf.storage_offset() + x.off) for x in xs]
+                    entries.append(LateralEntry.apply(ts[0], ts[1] if len(ts) == 2 else None, seq[0].weight, seq[0].bias,
+                                                      seq[1].weight if len(seq) == 3 else None))
+                m = y4[4]
+                y4 = [LateralBlock.apply(t, *getattr(self, "latlayer_%d" % k)[-1].tensors()) for k, t in enumerate(entries)]
+                y4.append(m.buf.view(m.N, m.T, m.H, m.W, m.ld))
+            elif what == "lateral_blocks":
                 # the entry convs' outputs: the four ConvNextBlocks run here, from the live tensors, and carry a graph
                 tensors = [s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4]
                 y4 = [LateralBlock.apply(t, *getattr(self, "latlayer_%d" % k)[-1].tensors()) for k, t in enumerate(tensors[:4])]
@@ -844,7 +864,7 @@ class AudioVisualSaliencyModel(_SaliencyBase):
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
                 masks = self.adapter.run(o1, o0)
-                pm = None if features in ("laterals", "entries") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
+                pm = None if features in ("laterals", "entries", "inputs") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             with fk.branch(1):
                 aud = self.audnet.forward_cl(audios.float())
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
@@ -912,7 +932,7 @@ class VisualSaliencyModel(_SaliencyBase):
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
                 masks = self.adapter.run(o1, o0)
-                pm = None if features in ("laterals", "entries") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
+                pm = None if features in ("laterals", "entries", "inputs") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
             cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3, features)
             s3 = self._lateral(pk, 3, [v4], features=features)
