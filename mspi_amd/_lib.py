@@ -305,6 +305,16 @@ _ENTRY_SIGNATURES = {
 
 ENTRY_EXPORTS = tuple(_ENTRY_SIGNATURES)
 
+# The adapter's weight gradient declared in include/mspi_adapter_train_hip.h (csrc/adapter_bwd.hip): a fifth table, likewise
+_ADAPTER_SIGNATURES = {
+    "mspi_conv_wgrad_t16_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "mspi_conv_wgrad_t16_ws_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "mspi_conv_wgrad_t16_variant": (C.c_int, [C.POINTER(ConvDesc), _P, _P]),
+    "mspi_conv_wgrad_t16": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
+}
+
+ADAPTER_EXPORTS = tuple(_ADAPTER_SIGNATURES)
+
 _lib = None
 
 
@@ -324,7 +334,7 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
-            list(_ENTRY_SIGNATURES.items()):
+            list(_ENTRY_SIGNATURES.items()) + list(_ADAPTER_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

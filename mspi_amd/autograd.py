@@ -233,8 +233,9 @@ class Fusion(torch.autograd.Function):
     conv_mask[0].bn.weight, conv_mask[0].bn.bias, conv_mask[2].weight, conv_mask[2].bias in their nn layouts.  bn_k:
     (running_mean, running_var, num_batches_tracked) of sa_k.conv_mask[0].bn, updated in place as nn.BatchNorm3d.train()
     with that layer's momentum 0.001 updates them, or None to skip that; the normalisation is on BATCH statistics either way.
-    Gradients: the 15 SA tensors and each lateral that requires grad; masks gets none (the adapter is frozen).  No double
-    backward."""
+    Gradients: the 15 SA tensors and each lateral that requires grad; masks when it requires grad (trainable("adapter")): the
+    data gradient of the concatenated 3x3x3 conv, one more launch -- with detached masks nothing more is launched and every
+    other gradient keeps its bits.  No double backward."""
 
     @staticmethod
     def forward(ctx, l0, l1, l2, l3, masks, *rest):
@@ -288,14 +289,14 @@ class Fusion(torch.autograd.Function):
                 gates.append(gate.buf)
         s2, s1, s0 = outs
         ctx.save_for_backward(lats[0], lats[1], lats[2], masks, pre.buf, pm.buf, mean, rstd, gamma, *ms[::-1], *gates[::-1],
-                              *[p[3] for p in sa])
+                              *[p[3] for p in sa], *[p[0] for p in sa])
         ctx.dims = (B, T, h, w, D, Cm, mid)
         return tuple(t.buf.view(t.N, t.T, t.H, t.W, t.ld) for t in (s0, s1, s2)) + (lats[3].clone(),)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, G0, G1, G2, G3):
-        l0, l1, l2, masks, preb, pmb, mean, rstd, gamma, m0b, m1b, m2b, g0b, g1b, g2b, w20, w21, w22 = ctx.saved_tensors
+        l0, l1, l2, masks, preb, pmb, mean, rstd, gamma, m0b, m1b, m2b, g0b, g1b, g2b, w20, w21, w22, wc0, wc1, wc2 = ctx.saved_tensors
         B, T, h, w, D, Cm, mid = ctx.dims
         need = ctx.needs_input_grad
         dev = l0.device
@@ -311,7 +312,7 @@ class Fusion(torch.autograd.Function):
         if need[3]:
             D3 = E.upsample_sum_bwd(_cl5(G[3].buf.view(B, T, h >> 3, w >> 3, D).clone()), [(G[1], 4), (D2, 2)], accumulate=True)
             grads[3] = D3.buf.view(B, T, h >> 3, w >> 3, D)
-        sa_need = any(need[5:20])
+        sa_need = any(need[4:20])                # the gradient of masks runs through the three gates as well
         dp = E.alloc(B, T, hm, wm, 3 * mid, dev)
         for k, (Gk, lk, mb, gb, w2) in enumerate(((G[0], l0, m0b, g0b, w20), (G[1], l1, m1b, g1b, w21), (D2, l2, m2b, g2b, w22))):
             if not (need[k] or sa_need):
@@ -350,6 +351,13 @@ class Fusion(torch.autograd.Function):
                 xs = _cl5(masks[..., c0:c0 + c].contiguous())
             parts.append(E.conv_wgrad_wide(xs, dpre, geo)[0])
         dW = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+        if need[4]:
+            # data gradient of the concatenated (3,3,3) conv Cm -> 3 mid: the same conv with w'[ci][-tap][co], on the fp32 MFMA
+            # path (ReadoutHead.backward)
+            wcat = torch.cat([wc0.detach(), wc1.detach(), wc2.detach()], 0)
+            pkt = E.pack_conv(wcat.transpose(0, 1).flip(2, 3, 4), None, None, (1, 1, 1), (1, 1, 1), E.ACT_NONE, prec=E.PREC_F32)
+            dm = E.conv(dpre, pkt)
+            grads[4] = dm.buf.view(B, T, hm, wm, dm.ld)
         for k in range(3):
             sl = slice(k * mid, (k + 1) * mid)
             grads[5 + 5 * k], grads[5 + 5 * k + 1], grads[5 + 5 * k + 2] = dW[sl], dgam[sl], dbet[sl]
@@ -597,3 +605,179 @@ class LateralEntry(torch.autograd.Function):
             dw0, db0 = out[:Ci].t()[:, :, None, None, None], out[Ci]
         grads = (None, None, dw0, db0, dw1)
         return tuple(gr if need[i] else None for i, gr in enumerate(grads))
+
+
+ADAPTER_LAYERS = ("b0", "b1a", "b1s", "b1t", "b2a", "b2s", "b2t", "b3")      # branch0 | branch1: 1x1x1, conv_s, conv_t | branch2 | branch3
+_ADAPTER_KERNEL = {"s": ((1, 3, 3), (0, 1, 1)), "t": ((3, 1, 1), (1, 0, 0))}
+_ADAPTER_CHAINS = (("b0",), ("b1a", "b1s", "b1t"), ("b2a", "b2s", "b2t"), ("b3",))
+BN_MAX_CH = 192                          # widest channel count the mspi_bn_* entry points take
+
+
+def _bn_slices(c):
+    """Channel slices the BatchNorm kernels take: the statistics are per channel, so a wider layer in slices is exact."""
+    if c <= BN_MAX_CH:
+        return [(0, c)]
+    n = -(-c // BN_MAX_CH)
+    step = (-(-c // n) + 3) // 4 * 4
+    return [(c0, min(step, c - c0)) for c0 in range(0, c, step)]
+
+
+def wgrad_wide_sliced(x, dy, k, pad):
+    """The weight gradient of a stride-1 conv from mspi_conv_wgrad_wide_fwd where both widths are multiples of 32: slices of at
+    most WGRAD_WIDE_MAX_CH channels of either, even ones, a slice of the wider tensor as it stands where the kernel accepts its
+    strides and a dense copy where it refuses (_wide_slices).  Returns dW [Co,Ci,kt,kh,kw]."""
+    def cut(c):
+        n = -(-c // WGRAD_WIDE_MAX_CH)
+        step = -(-c // n // 32) * 32
+        return [(c0, min(step, c - c0)) for c0 in range(0, c, step)]
+
+    def dense(t, c0, c):
+        return E.from_rows(t.as_rows()[:, c0:c0 + c].contiguous()).reshape(t.N, t.T, t.H, t.W)
+    rows = []
+    for o0, oc in cut(dy.C):
+        cols = []
+        for c0, cc in cut(x.C):
+            xs, ds, geo = x.slice(c0, cc), dy.slice(o0, oc), _geometry(k, pad, cc, oc)
+            if E.conv_wgrad_wide_variant(xs, ds, geo) < 0:
+                xs, ds = dense(x, c0, cc), dense(dy, o0, oc)
+            cols.append(E.conv_wgrad_wide(xs, ds, geo)[0])
+        rows.append(cols[0] if len(cols) == 1 else torch.cat(cols, 1))
+    return rows[0] if len(rows) == 1 else torch.cat(rows, 0)
+
+
+def adapter_wgrad_route(rows, cin, cout):
+    """"t16" or "wide": which kernel adapter_wgrad calls.  Measured on one MI355X (tools/adapter_bench.py,
+    profiles/r20_adapter.txt): at 2 688 rows (two clips) mspi_conv_wgrad_t16 is the faster on all three layers the wide kernel
+    takes (416 -> 192: 0.087 against 0.095 ms, 416 -> 96: 0.068 / 0.092, 416 -> 64: 0.060 / 0.099); at 10 752 rows (eight clips)
+    it LOSES on all three (0.165 / 0.110, 0.129 / 0.099, 0.114 / 0.101).  The switch sits at the row count from which the new
+    kernel takes its longest slices, between the two measured points; nothing in between was measured.  The other five layers
+    have widths the wide kernel refuses and go to the new kernel at every size."""
+    wide_takes = cin % 32 == 0 and cout % 32 == 0 and cout <= WGRAD_WIDE_MAX_CH
+    return "wide" if wide_takes and rows >= E.WGRAD_T16_ROWS[1] else "t16"
+
+
+def adapter_wgrad(x, dz, geo):
+    """The weight gradient of one adapter layer (no bias), by the route adapter_wgrad_route names."""
+    if adapter_wgrad_route(x.M, geo.cin, geo.cout) == "wide":
+        return wgrad_wide_sliced(x, dz, geo.k, geo.pad)
+    return E.conv_wgrad_t16(x, dz, geo)[0]
+
+
+class Adapter(torch.autograd.Function):
+    """masks = Adapter.apply(cat, *tensors, *bns): the adapter's Inception (Adapter.conv, backbones/s3d.py upstream) on cat, the
+    416-wide input Adapter.run assembles, channels-last fp32 [B,T,h,w,Cin] on the GPU.  tensors: for each of the eight layers in
+    ADAPTER_LAYERS order conv.weight, bn.weight, bn.bias in their nn layouts (24); bns: for each layer (running_mean,
+    running_var, num_batches_tracked), updated in place as nn.BatchNorm3d.train() with momentum 0.001 updates them, or None to
+    skip that; the normalisation is on BATCH statistics either way (eps 1e-3).  Every width a multiple of 16, Cin <= 416, the
+    others <= 208.  The forward runs, per layer, the unfolded conv, bn_stats and bn_apply with its ReLU -- layers wider than the
+    BatchNorm kernels take in channel slices of a strided view -- the four branches writing their slices of one output
+    [B,T,h,w,c0+c1+c2+c3]; branch3's 3x3x3 max-pool is forward only.  Backward per layer: bn_bwd under the ReLU mask, the weight
+    gradient (adapter_wgrad: mspi_conv_wgrad_t16, or from 8192 rows on mspi_conv_wgrad_wide_fwd on the three layers it takes and was
+    measured faster on), and through conv_t and conv_s the data gradient as the same conv on the flipped weights at
+    PREC_F32.  Gradients: the 24 tensors.  cat gets NONE: the image encoder is frozen, as upstream.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, cat, *rest):
+        if len(rest) != 32:
+            raise MspiError("Adapter: expected 24 tensors and 8 BatchNorm buffer triples after cat, got %d arguments" % len(rest))
+        if not cat.is_cuda:
+            raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % cat.device)
+        if cat.dim() != 5 or cat.dtype != torch.float32:
+            raise MspiError("Adapter: cat must be fp32 [B,T,h,w,C] (channels-last), got %s %s" % (cat.dtype, tuple(cat.shape)))
+        ps = {l: rest[3 * i:3 * i + 3] for i, l in enumerate(ADAPTER_LAYERS)}
+        bns = dict(zip(ADAPTER_LAYERS, rest[24:]))
+        B, T, h, w, cin = cat.shape
+        geos, src = {}, {}
+        for chain in _ADAPTER_CHAINS:
+            c = cin
+            for l in chain:
+                k, pad = _ADAPTER_KERNEL.get(l[2:], ((1, 1, 1), (0, 0, 0)))
+                wl, gam, bet = ps[l]
+                co = wl.shape[0] if wl.dim() == 5 else -1
+                if wl.dim() != 5 or tuple(wl.shape) != (co, c) + k or gam.numel() != co or bet.numel() != co or wl.device != cat.device:
+                    raise MspiError("Adapter: layer %s has conv.weight %s, BatchNorm %d / %d on %s; it reads %d channels through a "
+                                    "%s kernel on %s" % (l, tuple(wl.shape), gam.numel(), bet.numel(), wl.device, c, k, cat.device))
+                if c % 16 or co % 16 or c > E.WGRAD_T16_MAX_CIN or co > E.WGRAD_T16_MAX_COUT:
+                    raise MspiError("Adapter: layer %s is %d -> %d wide; the widths must be multiples of 16, at most %d in and %d out"
+                                    % (l, c, co, E.WGRAD_T16_MAX_CIN, E.WGRAD_T16_MAX_COUT))
+                geos[l], src[l] = (k, pad, c, co), (None if l == chain[0] else prev)
+                c, prev = co, l
+        widths = [geos[chain[-1]][3] for chain in _ADAPTER_CHAINS]
+        cat = cat.detach().contiguous()
+        saved, stats = [cat], {}
+        with torch.no_grad():
+            x0 = _cl5(cat)
+            pooled = E.maxpool(x0, (3, 3, 3), (1, 1, 1), (1, 1, 1))
+            out = E.alloc(B, T, h, w, sum(widths), cat.device)
+            ys, c0 = {}, 0
+            for chain, cw in zip(_ADAPTER_CHAINS, widths):
+                for l in chain:
+                    k, pad, _, co = geos[l]
+                    x = (pooled if l == "b3" else x0) if src[l] is None else ys[src[l]]
+                    z = E.conv(x, E.pack_conv(ps[l][0], None, None, (1, 1, 1), pad, E.ACT_NONE))
+                    y = out.slice(c0, co) if l == chain[-1] else E.alloc(B, T, h, w, co, cat.device)
+                    gam, bet = ps[l][1].detach().float().contiguous(), ps[l][2].detach().float().contiguous()
+                    mean, var, rstd = (torch.empty(co, dtype=torch.float32, device=cat.device) for _ in range(3))
+                    for s0, sc in _bn_slices(co):
+                        m_, v_, r_ = E.bn_stats(z.slice(s0, sc), SA_BN_EPS)
+                        E.bn_apply(z.slice(s0, sc), m_, r_, gam[s0:s0 + sc].contiguous(), bet[s0:s0 + sc].contiguous(), act=E.ACT_RELU,
+                                   out=y.slice(s0, sc))
+                        mean[s0:s0 + sc], var[s0:s0 + sc], rstd[s0:s0 + sc] = m_, v_, r_
+                    if bns[l] is not None:
+                        _bn_running(bns[l], mean, var, z.M, SA_BN_MOMENTUM)
+                    ys[l], stats[l] = y, (z.buf, mean, rstd, gam)
+                c0 += cw
+        for l in ADAPTER_LAYERS:
+            saved += [stats[l][0], ys[l].buf, stats[l][1], stats[l][2], stats[l][3], ps[l][0]]
+        ctx.save_for_backward(*saved, pooled.buf)
+        ctx.dims, ctx.geos, ctx.widths = (B, T, h, w), geos, widths
+        return out.buf.view(B, T, h, w, out.ld)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        saved = list(ctx.saved_tensors)
+        B, T, h, w = ctx.dims
+        geos, widths = ctx.geos, ctx.widths
+        need = ctx.needs_input_grad
+        grads = [None] * 33
+        if not any(need[1:25]):
+            return tuple(grads)
+        cat, pooled = saved[0], saved[-1]
+        Cm = sum(widths)
+
+        def cl(buf, c, ld=None, off=0):
+            return E.CL(buf.view(-1), off, B, T, h, w, c, c if ld is None else ld)
+        Gc = cl(G.float().contiguous(), Cm)
+        t = {l: saved[1 + 6 * i:7 + 6 * i] for i, l in enumerate(ADAPTER_LAYERS)}
+        c0 = 0
+        for chain, cw in zip(_ADAPTER_CHAINS, widths):
+            dy = Gc.slice(c0, cw)
+            for j in range(len(chain) - 1, -1, -1):
+                l = chain[j]
+                i = ADAPTER_LAYERS.index(l)
+                k, pad, c, co = geos[l]
+                zb, yb, mean, rstd, gam, wl = t[l]
+                z = cl(zb, co)
+                y = cl(yb, co, Cm, c0) if j == len(chain) - 1 else cl(yb, co)       # a branch's last output lies in its slice of masks
+                if not any(need[1 + 3 * i2] or need[2 + 3 * i2] or need[3 + 3 * i2] for i2 in (ADAPTER_LAYERS.index(q) for q in chain[:j + 1])):
+                    break                                                           # nothing further down this branch is asked for
+                dz = E.alloc(B, T, h, w, co, cat.device)
+                dgam, dbet = (torch.empty(co, dtype=torch.float32, device=cat.device) for _ in range(2))
+                for s0, sc in _bn_slices(co):
+                    _, dg, dbt = E.bn_bwd(dy.slice(s0, sc), z.slice(s0, sc), mean[s0:s0 + sc].contiguous(), rstd[s0:s0 + sc].contiguous(),
+                                          gam[s0:s0 + sc].contiguous(), y=y.slice(s0, sc), dx=dz.slice(s0, sc))
+                    dgam[s0:s0 + sc], dbet[s0:s0 + sc] = dg, dbt
+                if j == 0:
+                    x = cl(pooled, c) if l == "b3" else cl(cat, c)
+                else:
+                    x = cl(t[chain[j - 1]][1], c)
+                grads[1 + 3 * i] = adapter_wgrad(x, dz, _geometry(k, pad, c, co)).contiguous()
+                grads[2 + 3 * i], grads[3 + 3 * i] = dgam, dbet
+                if j:
+                    # data gradient of a stride-1 "same" conv: the same conv with w'[ci][-tap][co], on the fp32 MFMA path
+                    # (ReadoutTail.backward)
+                    dy = E.conv(dz, E.pack_conv(wl.detach().transpose(0, 1).flip(2, 3, 4), None, None, (1, 1, 1), pad, E.ACT_NONE,
+                                                prec=E.PREC_F32))
+            c0 += cw
+        return tuple(g if g is None or need[i] else None for i, g in enumerate(grads))

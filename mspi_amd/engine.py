@@ -26,7 +26,8 @@ __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedC
            "layernorm", "attention", "upsample", "upsample_sum", "rowgate", "logsumexp_sub", "mean_rows", "neg_cosine", "se_gate",
            "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "conv_wgrad_wide",
            "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "rowgate_bwd", "upsample_sum_bwd", "gelu_bwd",
-           "layernorm_bwd", "dwconv_wgrad", "conv_wgrad_entry", "conv_wgrad_entry_variant", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "layernorm_bwd", "dwconv_wgrad", "conv_wgrad_entry", "conv_wgrad_entry_variant", "conv_wgrad_t16",
+           "conv_wgrad_t16_variant", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 # ----------------------------------------------------------------------------- conv autotuning
@@ -1212,9 +1213,10 @@ def bn_apply(x, mean, rstd, gamma, beta, act=ACT_NONE, out=None):
     return out
 
 
-def bn_bwd(dy, x, mean, rstd, gamma, y=None):
+def bn_bwd(dy, x, mean, rstd, gamma, y=None, dx=None):
     """Backward of bn_apply(x, ...) on batch statistics for the output gradient dy; y: the forward's post-ReLU output when
-    it ran with ACT_RELU (the mask), None otherwise.  Returns (dx, dgamma, dbeta): a CL like x and two fp32 [C]."""
+    it ran with ACT_RELU (the mask), None otherwise.  Returns (dx, dgamma, dbeta): a CL like x (a new one, or dx: e.g. a channel
+    slice of a wider buffer) and two fp32 [C]."""
     lib = _lib.load()
     _need_gpu(x.buf)
     M, Cc = _bn_rows("bn_bwd", x)
@@ -1223,7 +1225,10 @@ def bn_bwd(dy, x, mean, rstd, gamma, y=None):
         if t is not None and ((t.M, t.C) != (M, Cc) or not t.dense or t.buf.device != dev):
             raise MspiError("bn_bwd: dy and y must match x (%d rows x %d channels, dense)" % (M, Cc))
     ptrs = [_bn_vec("bn_bwd", n, t, Cc, dev) for n, t in (("mean", mean), ("rstd", rstd), ("gamma", gamma))]
-    dx = alloc(x.N, x.T, x.H, x.W, x.C, dev)
+    if dx is None:
+        dx = alloc(x.N, x.T, x.H, x.W, x.C, dev)
+    elif (dx.M, dx.C) != (M, Cc) or not dx.dense or dx.buf.device != dev:
+        raise MspiError("bn_bwd: dx must match x (%d rows x %d channels, dense)" % (M, Cc))
     dgb = torch.empty(2, Cc, dtype=torch.float32, device=dev)
     ws = torch.empty(lib.mspi_bn_ws_bytes(M, Cc) // 4, dtype=torch.float32, device=dev)                     # stream-ordered
     with _Timed("bn_bwd", 8.0 * M * Cc, 4.0 * M * Cc * (6 if y is not None else 4), "M=%d C=%d" % (M, Cc)):
@@ -1391,6 +1396,43 @@ def conv_wgrad_entry(x, dy, pk):
         check(lib.mspi_conv_wgrad_entry(C.byref(d), x.ptr, dy.ptr, dW.data_ptr(), db.data_ptr(), ws.data_ptr(), _stream()),
               "mspi_conv_wgrad_entry")
     return dW[:pk.cout, :, :, :, :pk.cin].permute(0, 4, 1, 2, 3), db[:pk.cout]
+
+
+# ----------------------------------------------------------------------------- adapter (csrc/adapter_bwd.hip)
+WGRAD_T16_SLICES = (64, 128, 256)       # rows per slice: the codes mspi_conv_wgrad_t16_variant answers
+WGRAD_T16_ROWS = (1024, 8192)           # rows from which the second and the third are taken
+WGRAD_T16_MAX_CIN, WGRAD_T16_MAX_COUT = 416, 208
+
+
+def conv_wgrad_t16_variant(x, dy, pk):
+    """The instantiation conv_wgrad_t16(x, dy, pk) launches (rows per slice), -1 where it refuses; host only."""
+    return _lib.load().mspi_conv_wgrad_t16_variant(C.byref(_wgrad_desc(x, dy, pk)), x.ptr, dy.ptr)
+
+
+def conv_wgrad_t16(x, dy, pk, bias=False):
+    """conv_wgrad on 16 x 16 tiles for the adapter's layers: a stride-1 "same" conv (1,1,1), (1,3,3) or (3,1,1), stored Cin a
+    multiple of 16 up to 416, stored Cout a multiple of 16 up to 208; x and dy may be channel slices of wider buffers.  pk gives
+    the layer's geometry only.  Returns (dW [Co,Ci,kt,kh,kw], db [Co] or None without bias)."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    if x.Cs != pk.cin_s or dy.Cs != pk.cout_s:
+        raise MspiError("conv_wgrad_t16: x has %d / dy %d stored channels, the layer %d -> %d" % (x.Cs, dy.Cs, pk.cin_s, pk.cout_s))
+    d = _wgrad_desc(x, dy, pk)
+    if not dy.dense or dy.M != x.M or dy.buf.device != x.buf.device:
+        raise MspiError("conv_wgrad_t16: dy has %d rows, the layer's output %d (or dy has a sample stride of its own)" % (dy.M, x.M))
+    if lib.mspi_conv_wgrad_t16_variant(C.byref(d), x.ptr, dy.ptr) < 0:
+        raise MspiError("conv_wgrad_t16: %s" % lib.mspi_last_error().decode("utf-8", "replace"))
+    dev = x.buf.device
+    kt, kh, kw = pk.k
+    dW = torch.empty(pk.cout_s, kt, kh, kw, pk.cin_s, dtype=torch.float32, device=dev)
+    db = torch.empty(pk.cout_s, dtype=torch.float32, device=dev) if bias else None
+    ws = torch.empty(lib.mspi_conv_wgrad_t16_ws_bytes(C.byref(d)) // 4, dtype=torch.float32, device=dev)     # stream-ordered
+    taps = kt * kh * kw
+    with _Timed("conv_wgrad_t16", 2.0 * dy.M * taps * pk.cin * pk.cout, 4.0 * dy.M * (pk.cin + pk.cout),
+                "M=%d K=%d(%dx%d) N=%d" % (dy.M, taps * pk.cin, taps, pk.cin, pk.cout)):
+        check(lib.mspi_conv_wgrad_t16(C.byref(d), x.ptr, dy.ptr, dW.data_ptr(), db.data_ptr() if bias else None, ws.data_ptr(),
+                                      _stream()), "mspi_conv_wgrad_t16")
+    return dW.permute(0, 4, 1, 2, 3), db
 
 
 def mean_rows(x, N, R, out):

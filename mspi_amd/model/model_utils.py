@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from .. import engine as E
 from .._lib import MspiError
+from ..autograd import Adapter as AdapterTrain
 from ..autograd import (Fusion, LateralBlock, LateralEntry, ReadoutHead, ReadoutTail, compose_lateral, convnext_block_forward,
                         pack_convnext_block, pack_lateral_entry, pack_readout_tail, r0_parts, readout_tail_forward)
 from ..backbones.convnext import ConvNeXtTinyFeatures
@@ -225,8 +226,26 @@ class Adapter(HipModule):
         self.conv = Inception(embed_dim=embed_dim)
         self.up = nn.Upsample(scale_factor=(1, 2, 2), align_corners=False, mode="trilinear")
 
-    def run(self, o3, o2):
-        """o3 CL [(b t),1,h,w,96], o2 CL [(b t),1,h/2,w/2,320] -> masks CL [B,T/stride,h,w,512]."""
+    def tensors(self):
+        """The 24 tensors in the order of autograd.Adapter's arguments and the eight BatchNorm buffer triples behind them."""
+        ts, bns = [], []
+        for conv, bn in self.layers().values():
+            ts += [conv.weight, bn.weight, bn.bias]
+            bns.append((bn.running_mean, bn.running_var, bn.num_batches_tracked))
+        return ts, bns
+
+    def layers(self):
+        """{name of the BatchNorm module below the adapter: (conv, bn)} in autograd.ADAPTER_LAYERS order."""
+        c = self.conv
+        b1, b2 = c.branch1, c.branch2
+        return {"conv.branch0.0.bn": (c.branch0[0].conv, c.branch0[0].bn), "conv.branch1.0.bn": (b1[0].conv, b1[0].bn),
+                "conv.branch1.1.bn_s": (b1[1].conv_s, b1[1].bn_s), "conv.branch1.1.bn_t": (b1[1].conv_t, b1[1].bn_t),
+                "conv.branch2.0.bn": (b2[0].conv, b2[0].bn), "conv.branch2.1.bn_s": (b2[1].conv_s, b2[1].bn_s),
+                "conv.branch2.1.bn_t": (b2[1].conv_t, b2[1].bn_t), "conv.branch3.1.bn": (c.branch3[1].conv, c.branch3[1].bn)}
+
+    def run(self, o3, o2, features=False):
+        """o3 CL [(b t),1,h,w,96], o2 CL [(b t),1,h/2,w/2,320] -> masks CL [B,T/stride,h,w,512]; features == "cat" stops in
+        front of the Inception and returns its 416-wide input for autograd.Adapter."""
         T, s = self.num_frames, self.stride
         B = o3.N // T
         o3 = o3.reshape(B, T, o3.H, o3.W)
@@ -234,7 +253,7 @@ class Adapter(HipModule):
         cat = E.alloc(B, T // s, o3.H, o3.W, o3.C + o2.C, o3.buf.device)
         E.maxpool(o3, (s, 1, 1), (s, 1, 1), (0, 0, 0), out=cat.slice(0, o3.C))
         E.upsample(E.maxpool(o2, (s, 1, 1), (s, 1, 1), (0, 0, 0)), 2, dst=cat.slice(o3.C, o2.C))
-        return self.conv.run(cat)
+        return cat if features == "cat" else self.conv.run(cat)
 
 
 class LayerNorm3d(nn.Module):
@@ -442,7 +461,7 @@ class _SaliencyBase(HipModule):
         """latlayer_k: the entry conv(s), then the ConvNextBlock -- left to autograd.LateralBlock when features == "entries";
         features == "inputs" stops in front of the entry conv(s) and returns the encoder map(s) for autograd.LateralEntry, split
         planes joined into fp32 rows."""
-        if features == "inputs":
+        if features in ("inputs", "cat"):
             return [E.join_planes(x) if isinstance(x, E.SP) else x for x in xs]
         y = E.conv(xs[0], pk["lat"][k][0])
         if len(xs) == 2:
@@ -492,7 +511,8 @@ class _SaliencyBase(HipModule):
         and returns y4 [B,4,h,w,64]; "maps" stops in front of readout[0]; "laterals" in front of the gating (pm is None then);
         "entries" likewise, s0..s3 then being the entry convs' outputs (_lateral); "inputs" likewise, s0..s3 being the lists of
         encoder maps the entry convs read."""
-        if features in ("laterals", "entries", "inputs"):
+        if features in ("laterals", "entries", "inputs", "cat"):
+            # trainable("adapter"): as "inputs", and masks is the Inception's input, for autograd.Adapter;
             # trainable("fusion"): autograd.Fusion takes over from here, then ReadoutHead; trainable("lateral_blocks"): s0..s3
             # are the entry convs' outputs, and autograd.LateralBlock comes first; trainable("lateral_entries"): the entry
             # convs' inputs, and autograd.LateralEntry comes before that
@@ -569,9 +589,9 @@ class _SaliencyBase(HipModule):
             self.__dict__.pop("_pk", None)
             return
         with torch.no_grad():
-            if grad_tail not in ("laterals", "entries", "inputs"):    # ... autograd.Fusion for the SA fold, whose premask that forward does not launch
+            if grad_tail not in ("laterals", "entries", "inputs", "cat"):    # ... autograd.Fusion for the SA fold, whose premask that forward does not launch
                 self._refresh_sa(pk)
-            if grad_tail not in ("maps", "laterals", "entries", "inputs"):
+            if grad_tail not in ("maps", "laterals", "entries", "inputs", "cat"):
                 self._refresh_head(pk)
             if not grad_tail:          # ... and ReadoutTail does the same for the tail
                 self._refresh_tail(pk)
@@ -603,7 +623,13 @@ class _SaliencyBase(HipModule):
     TAIL_PARAMS = tuple("readout.%d.%s" % (i, n) for i in (8, 10, 12) for n in ("weight", "bias"))
 
     def trainable(self, what):
-        """trainable("lateral_entries"): on top of what "lateral_blocks" trains, the laterals' entry convs -- latlayer_k[0]
+        """trainable("adapter"): on top of what "lateral_entries" trains, the adapter's Inception -- the eight conv -> BatchNorm3d
+        -> ReLU layers of adapter.conv, 24 more tensors: 107 in all with the all-composed encoders, 105 with s3d, 103 with
+        slowfast.  A forward with grad enabled stops the image branch IN FRONT of the Inception and hands its 416-wide input to
+        autograd.Adapter (the eight layers on BATCH statistics, 13 such layers in all), whose masks carry a graph into
+        autograd.Fusion, which then returns their gradient.  That input gets no gradient.  Still frozen: the SyncBlock, the
+        contrastive projectors and every encoder.
+        trainable("lateral_entries"): on top of what "lateral_blocks" trains, the laterals' entry convs -- latlayer_k[0]
         (1x1x1, weight and bias) and, where cfg.MODEL.LATERAL_BOOL[k] is set, latlayer_k[1] ((s,1,1) / stride (s,1,1), weight):
         12 more tensors with the all-composed encoders (83 in all), 10 with s3d (81), 8 with slowfast (79).  A forward with grad
         enabled stops each lateral IN FRONT of its entry conv(s) and hands the encoder maps to autograd.LateralEntry, then to
@@ -633,10 +659,10 @@ class _SaliencyBase(HipModule):
                 p.requires_grad_(flag)
             d["_trainable"] = None
             return self
-        if what not in ("readout_tail", "readout", "fusion", "lateral_blocks", "lateral_entries"):
+        if what not in ("readout_tail", "readout", "fusion", "lateral_blocks", "lateral_entries", "adapter"):
             raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail', 'readout', 'fusion', "
-                            "'lateral_blocks' and 'lateral_entries' are)" % (what,))
-        if what in ("readout", "fusion", "lateral_blocks", "lateral_entries") and not DECODER_FUSED:
+                            "'lateral_blocks', 'lateral_entries' and 'adapter' are)" % (what,))
+        if what in ("readout", "fusion", "lateral_blocks", "lateral_entries", "adapter") and not DECODER_FUSED:
             raise MspiError("trainable(%r) needs the fused decoder path: it is switched off by MSPI_DECODER_FUSED=0" % (what,))
         if d.get("_trainable") is None:
             d["_trainable_saved"] = [(p, p.requires_grad) for p in self.parameters()]
@@ -644,7 +670,9 @@ class _SaliencyBase(HipModule):
         tail = set(self.TAIL_PARAMS)
         blocks = tuple("latlayer_%d.%d." % (k, len(getattr(self, "latlayer_%d" % k)) - 1) for k in range(4))
         for name, p in self.named_parameters():
-            if what == "lateral_entries":      # every tensor of the four laterals
+            if what == "adapter":              # ... and the adapter's Inception
+                p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.", "latlayer_", "adapter.")))
+            elif what == "lateral_entries":    # every tensor of the four laterals
                 p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.", "latlayer_")))
             elif what == "lateral_blocks":
                 p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.") + blocks))
@@ -658,10 +686,12 @@ class _SaliencyBase(HipModule):
         """{name: module} of the BatchNorm layers that run on batch statistics under the present switch."""
         what = self.__dict__.get("_trainable")
         mods = {}
-        if what in ("readout", "fusion", "lateral_blocks", "lateral_entries"):
+        if what in ("readout", "fusion", "lateral_blocks", "lateral_entries", "adapter"):
             mods.update({"readout.2": self.readout[2], "readout.5": self.readout[5]})
-        if what in ("fusion", "lateral_blocks", "lateral_entries"):        # LayerNorm has no mode, convs neither: the laterals add nothing
+        if what in ("fusion", "lateral_blocks", "lateral_entries", "adapter"):   # LayerNorm has no mode, convs neither: the laterals add nothing
             mods.update({"sa_%d.conv_mask.0.bn" % k: getattr(self, "sa_%d" % k).conv_mask[0].bn for k in range(3)})
+        if what == "adapter":              # the Inception's eight
+            mods.update({"adapter.%s" % n: bn for n, (_, bn) in self.adapter.layers().items()})
         return mods
 
     def _training_tail(self):
@@ -669,11 +699,13 @@ class _SaliencyBase(HipModule):
         (the four pyramid maps, for autograd.ReadoutHead and then ReadoutTail), "laterals" (the lateral outputs and the masks,
         for autograd.Fusion in front of those two), "entries" (the laterals' entry-conv outputs and the masks, for
         autograd.LateralBlock in front of those three), "inputs" (the encoder maps the entry convs read and the masks, for
-        autograd.LateralEntry in front of those four) or False."""
+        autograd.LateralEntry in front of those four), "cat" (the same with the Inception's input in the place of the masks, for
+        autograd.Adapter beside those) or False."""
         what = self.__dict__.get("_trainable")
         if what is None or not torch.is_grad_enabled():
             return False
-        return {"readout": "maps", "fusion": "laterals", "lateral_blocks": "entries", "lateral_entries": "inputs"}.get(what, True)
+        return {"readout": "maps", "fusion": "laterals", "lateral_blocks": "entries", "lateral_entries": "inputs",
+                "adapter": "cat"}.get(what, True)
 
     def _check_eval(self):
         """The forward's guard.  Under trainable("readout") exactly readout[2] and readout[5] may be in train() (they run on
@@ -681,7 +713,7 @@ class _SaliencyBase(HipModule):
         under trainable("lateral_blocks") and trainable("lateral_entries") the same five; any other module in train() is refused by name, as the model itself is."""
         super()._check_eval()
         what = self.__dict__.get("_trainable")
-        if what not in ("readout", "fusion", "lateral_blocks", "lateral_entries"):
+        if what not in ("readout", "fusion", "lateral_blocks", "lateral_entries", "adapter"):
             return
         allowed = {id(m) for m in self._batch_stat_modules().values()}
         for name, mod in self.named_modules():
@@ -692,6 +724,10 @@ class _SaliencyBase(HipModule):
                 if what == "lateral_blocks":
                     raise MspiError("%s.%s is in train() mode: under trainable('lateral_blocks') only readout.2, readout.5 and "
                                     "the three sa_k.conv_mask.0.bn run on batch statistics (the blocks' LayerNorm has no mode); "
+                                    "call frozen_encoder()" % (type(self).__name__, name))
+                if what == "adapter":
+                    raise MspiError("%s.%s is in train() mode: under trainable('adapter') only readout.2, readout.5, the three "
+                                    "sa_k.conv_mask.0.bn and the eight BatchNorm layers of adapter.conv run on batch statistics; "
                                     "call frozen_encoder()" % (type(self).__name__, name))
                 if what == "lateral_entries":
                     raise MspiError("%s.%s is in train() mode: under trainable('lateral_entries') only readout.2, readout.5 and "
@@ -721,7 +757,7 @@ class _SaliencyBase(HipModule):
                 raise MspiError("trainable('%s'): a forward with grad runs %s on batch statistics, but in eval() mode the "
                                 "no_grad forward folds the running ones; call frozen_encoder() (engine_train.train_one_epoch does)"
                                 % (what, ", ".join(idle)))
-            if what == "lateral_entries":
+            if what in ("lateral_entries", "adapter"):
                 # the encoder maps: the entry convs run here, from the live tensors, and their outputs carry a graph
                 entries = []
                 for k, xs in enumerate(y4[:4]):
@@ -732,7 +768,12 @@ class _SaliencyBase(HipModule):
                                                       seq[1].weight if len(seq) == 3 else None))
                 m = y4[4]
                 y4 = [LateralBlock.apply(t, *getattr(self, "latlayer_%d" % k)[-1].tensors()) for k, t in enumerate(entries)]
-                y4.append(m.buf.view(m.N, m.T, m.H, m.W, m.ld))
+                m = m.buf.view(m.N, m.T, m.H, m.W, m.ld)
+                if what == "adapter":
+                    # the Inception's input: its eight layers run here, from the live tensors, and the masks carry a graph
+                    ts, bns = self.adapter.tensors()
+                    m = AdapterTrain.apply(m, *ts, *bns)
+                y4.append(m)
             elif what == "lateral_blocks":
                 # the entry convs' outputs: the four ConvNextBlocks run here, from the live tensors, and carry a graph
                 tensors = [s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4]
@@ -863,8 +904,8 @@ class AudioVisualSaliencyModel(_SaliencyBase):
         with _Fork(self, dev) as fk:
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
-                masks = self.adapter.run(o1, o0)
-                pm = None if features in ("laterals", "entries", "inputs") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
+                masks = self.adapter.run(o1, o0, features)   # "cat": the Inception's input, for autograd.Adapter
+                pm = None if features in ("laterals", "entries", "inputs", "cat") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             with fk.branch(1):
                 aud = self.audnet.forward_cl(audios.float())
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
@@ -931,8 +972,8 @@ class VisualSaliencyModel(_SaliencyBase):
         with _Fork(self, clips.device) as fk:
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
-                masks = self.adapter.run(o1, o0)
-                pm = None if features in ("laterals", "entries", "inputs") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
+                masks = self.adapter.run(o1, o0, features)   # "cat": the Inception's input, for autograd.Adapter
+                pm = None if features in ("laterals", "entries", "inputs", "cat") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
             cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3, features)
             s3 = self._lateral(pk, 3, [v4], features=features)

@@ -1,6 +1,6 @@
 """Fine-tune the readout (or only its tail, or the SA gates with it) of a checkpoint: the reference's train.py as far as the readout needs it, on the MI355X.
 
-    python -m mspi_amd.train --trainable readout|readout_tail|fusion|lateral_blocks|lateral_entries --weights w.pt --dataset AVAD --split 1 --model x3dl
+    python -m mspi_amd.train --trainable readout|readout_tail|fusion|lateral_blocks|lateral_entries|adapter --weights w.pt --dataset AVAD --split 1 --model x3dl
         [--path_data ./AuViDataset] [--log_dir ./training_logs] [--save_ckpt_freq 10] [--gamma 1] [--start_epoch 0]
         [--resolution H W] [--batch 2] [--no_sound] [--workers 8]
 
@@ -15,9 +15,12 @@ the depthwise convs', LayerNorm's and GELU's backward); the laterals' entry conv
 --trainable lateral_entries: on top of that the laterals' entry convs train, latlayer_k[0] and where present latlayer_k[1] --
 83 tensors with x3dl, 81 with s3d, 79 with slowfast (autograd.LateralEntry: the weight gradient of the composed conv, then the
 chain rule through the composition); with it every lateral parameter moves, as in upstream's training.
-Still frozen in all five: the adapter (and the gradient of its masks), the SyncBlock and every encoder (below --trainable
-lateral_entries also the laterals' entry convs, with --trainable fusion also the laterals' blocks, with --trainable readout and
-readout_tail also the SA gating).  That is fine-tuning of a released checkpoint's decoder head, not upstream's full training.  As upstream: the training split of
+--trainable adapter: on top of that the adapter's Inception trains, its eight conv -> BatchNorm -> ReLU layers on batch
+statistics -- 107 tensors with x3dl, 105 with s3d, 103 with slowfast (autograd.Adapter; autograd.Fusion returns the gradient
+of the masks); with it the visual-only model trains everything upstream trains except the motion encoder.
+Still frozen in all six: the SyncBlock, the contrastive projectors and every encoder (below --trainable adapter also the
+adapter, below --trainable lateral_entries also the laterals' entry convs, with --trainable fusion also the laterals' blocks,
+with --trainable readout and readout_tail also the SA gating).  That is fine-tuning of a released checkpoint's decoder head, not upstream's full training.  As upstream: the training split of
 avsp_dataloader.AudioVisualDataset, AdamW over the parameters that require grad with weight decay 0, cfg.SOLVER.LR for 60
 epochs then a tenth of it every 60 (lr_by_epoch), a state_dict checkpoint every --save_ckpt_freq epochs and at the end
 (inference.build_model loads them), one JSON line per epoch, printed and appended to <log_dir>/log.txt.  One process, one GPU."""
@@ -32,7 +35,8 @@ from ._lib import MspiError
 TRAINABLE = ("readout_tail", "readout")           # what trains on a frozen pyramid
 TRAINABLE_STAGES = TRAINABLE + ("fusion",)        # ... and on frozen laterals
 TRAINABLE_BLOCKS = ("lateral_blocks",)            # ... and with the laterals' ConvNextBlocks
-TRAINABLE_ENTRIES = ("lateral_entries",)          # ... and with the laterals' entry convs: every value --trainable takes
+TRAINABLE_ENTRIES = ("lateral_entries",)          # ... and with the laterals' entry convs
+TRAINABLE_ADAPTER = ("adapter",)                  # ... and with the adapter's Inception: every value --trainable takes
 
 
 def lr_by_epoch(cfg):
@@ -53,17 +57,19 @@ def _single_rank():
 
 
 def check_trainable(value):
-    if value not in TRAINABLE_STAGES + TRAINABLE_BLOCKS + TRAINABLE_ENTRIES:
+    if value not in TRAINABLE_STAGES + TRAINABLE_BLOCKS + TRAINABLE_ENTRIES + TRAINABLE_ADAPTER:
         raise MspiError("--trainable %s: only %s can be trained on a frozen pyramid, and %s on frozen laterals, and %s on frozen "
-                        "entry convs, and %s on frozen encoders (the models' backward stops behind the laterals' entry convs: "
-                        "the adapter, the SyncBlock and the encoders do not train)"
-                        % (value, ", ".join(TRAINABLE), TRAINABLE_STAGES[-1], ", ".join(TRAINABLE_BLOCKS), ", ".join(TRAINABLE_ENTRIES)))
+                        "entry convs, and %s on a frozen adapter, and %s on frozen encoders (the models' backward stops behind the "
+                        "laterals' entry convs and the adapter's Inception: the SyncBlock, the contrastive projectors and the "
+                        "encoders do not train)"
+                        % (value, ", ".join(TRAINABLE), TRAINABLE_STAGES[-1], ", ".join(TRAINABLE_BLOCKS), ", ".join(TRAINABLE_ENTRIES),
+                           ", ".join(TRAINABLE_ADAPTER)))
     return value
 
 
 def build_parser():
     parser = argparse.ArgumentParser(prog="python -m mspi_amd.train", description=__doc__.split("\n")[0])
-    parser.add_argument("--trainable", default="readout_tail", type=str, help="the part of the model that trains: readout_tail, readout, fusion, lateral_blocks or lateral_entries")
+    parser.add_argument("--trainable", default="readout_tail", type=str, help="the part of the model that trains: readout_tail, readout, fusion, lateral_blocks, lateral_entries or adapter")
     parser.add_argument("--start_epoch", default=0, type=int)
     parser.add_argument("--split", default=1, type=int)
     parser.add_argument("--dataset", default="AVAD", type=str)
@@ -89,7 +95,8 @@ def train(model, data, cfg, device, log_dir, start_epoch=0, save_ckpt_freq=10, g
     params = [p for p in model.parameters() if p.requires_grad]
     if not params:
         raise MspiError("train: no parameter requires grad; call model.trainable('readout_tail'), model.trainable('readout'), "
-                        "model.trainable('fusion'), model.trainable('lateral_blocks') or model.trainable('lateral_entries') first")
+                        "model.trainable('fusion'), model.trainable('lateral_blocks'), model.trainable('lateral_entries') or "
+                        "model.trainable('adapter') first")
     optimizer = torch.optim.AdamW(params, cfg.SOLVER.LR, weight_decay=0)
     schedule = lr_by_epoch(cfg)
     ckpt_dir = os.path.join(log_dir, "checkpoints")
