@@ -18,10 +18,72 @@ block's ten tensors.  Its output is one of Fusion's laterals.
 LateralEntry: the entry conv(s) in front of that block -- latlayer_k[0], 1x1x1 C_k -> 192 with bias, and where present
 latlayer_k[1], (s,1,1) / stride (s,1,1) 192 -> 192 without bias, run composed as one conv (compose_lateral) -- over the
 encoder map(s).  Its output is LateralBlock's input, whose gradient LateralBlock computes when it is asked for."""
+import collections
+
 import torch
 
 from . import engine as E
 from ._lib import MspiError
+
+# The training stages, each on top of the one before: the one place a new stage is added.  stop: what _training_tail() answers
+# and the forward stops at; params: the parameter-name prefixes the stage adds ({k}, {last}: each lateral and the index of its
+# ConvNextBlock); batch_stat: the BatchNorm modules it puts on batch statistics; only: what _check_eval says may be in train().
+Stage = collections.namedtuple("Stage", "name stop params batch_stat only")
+_SA_BN = tuple("sa_%d.conv_mask.0.bn" % k for k in range(3))
+_ADAPTER_BN = tuple("adapter.conv.branch%s" % n for n in ("0.0.bn", "1.0.bn", "1.1.bn_s", "1.1.bn_t", "2.0.bn", "2.1.bn_s", "2.1.bn_t",
+                                                         "3.1.bn"))        # ADAPTER_LAYERS order
+_ONLY5 = "only readout.2, readout.5 and the three sa_k.conv_mask.0.bn run on batch statistics"
+STAGES = (
+    Stage("readout_tail", True, tuple("readout.%d.%s" % (i, n) for i in (8, 10, 12) for n in ("weight", "bias")), (), None),
+    Stage("readout", "maps", ("readout.",), ("readout.2", "readout.5"), "only readout.2 and readout.5 run on batch statistics"),
+    Stage("fusion", "laterals", ("sa_0.", "sa_1.", "sa_2."), _SA_BN, _ONLY5),
+    Stage("lateral_blocks", "entries", ("latlayer_{k}.{last}.",), (), _ONLY5 + " (the blocks' LayerNorm has no mode)"),
+    Stage("lateral_entries", "inputs", ("latlayer_",), (),
+          _ONLY5 + " (neither the entry convs nor the blocks' LayerNorm have a mode)"),
+    Stage("adapter", "cat", ("adapter.",), _ADAPTER_BN,
+          "only readout.2, readout.5, the three sa_k.conv_mask.0.bn and the eight BatchNorm layers of adapter.conv run on batch "
+          "statistics"),
+)
+STAGE_NAMES = tuple(s.name for s in STAGES)
+
+
+def stage_rank(x):
+    """The ladder position of a stage name or of a stop value (what _training_tail() answers); -1 for None and False."""
+    if x is None or x is False:
+        return -1
+    return next(i for i, s in enumerate(STAGES) if x == s.name or x == s.stop)
+
+
+def reaches(x, name):
+    """True where x, a stage name or a stop value, is the stage `name` or one above it."""
+    return stage_rank(x) >= STAGE_NAMES.index(name)
+
+
+def stages_upto(what):
+    """The stages trainable(what) switches on, lowest first."""
+    return STAGES[:stage_rank(what) + 1]
+
+
+def _check_input(t, what=None, layout="[B,T,h,w,C]", beside=None):
+    """The refusals a Function opens with: a tensor off the GPU (or `beside` on another device), and, with what = "Function:
+    name", one that is not fp32 with five dimensions."""
+    if not t.is_cuda or (beside is not None and beside.device != t.device):
+        raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % t.device)
+    if what is not None and (t.dim() != 5 or t.dtype != torch.float32):
+        raise MspiError("%s must be fp32 %s (channels-last), got %s %s" % (what, layout, t.dtype, tuple(t.shape)))
+
+
+def _pack_dgrad(w, pad):
+    """The data gradient of a stride-1 "same" conv is the same conv with w'[ci][-tap][co] (a flip over an extent of 1 is the
+    identity, so one flip serves the (1,3,3) layers too).  On the fp32 MFMA path: the activation operand is a gradient, whose
+    scale is the loss's (1e-5 and below with SalLoss at the training shape), and the f16x3 split of an activation is exact only
+    while its largest entries stay above about 2^-5."""
+    return E.pack_conv(w.detach().transpose(0, 1).flip(2, 3, 4), None, None, (1, 1, 1), pad, E.ACT_NONE, prec=E.PREC_F32)
+
+
+def _pack_t(w):
+    """The transposed 1x1x1 conv (or 2-D weight) for a data gradient, on the fp32 MFMA path as in _pack_dgrad."""
+    return E.pack_conv(w.detach().flatten(1).t().contiguous(), None, prec=E.PREC_F32)
 
 
 def pack_readout_tail(w8, b8, w10, b10, w12, b12):
@@ -50,8 +112,7 @@ class ReadoutTail(torch.autograd.Function):
     def forward(ctx, y4, w8, b8, w10, b10, w12, b12):
         if y4.dim() != 5 or y4.shape[1] != 4 or y4.shape[4] != 64 or y4.dtype != torch.float32:
             raise MspiError("ReadoutTail: y4 must be fp32 [B,4,h,w,64] (channels-last), got %s" % (tuple(y4.shape),))
-        if not y4.is_cuda:
-            raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % y4.device)
+        _check_input(y4)
         y4 = y4.detach().contiguous()
         B, _, h, w, _ = y4.shape
         with torch.no_grad():
@@ -83,12 +144,7 @@ class ReadoutTail(torch.autograd.Function):
             grads[3], grads[4] = (dw10 if need[3] else None), (db10 if need[4] else None)
         if not any(need[:3]):
             return tuple(grads)
-        # data gradient of a stride-1 "same" conv: the same conv with w'[ci][-tap][co].  Both data-gradient convs run on the
-        # fp32 MFMA path: their activation operand is a gradient, whose scale is the loss's (1e-5 and below with SalLoss at the
-        # training shape), and the f16x3 split of an activation is exact only while its largest entries stay above about 2^-5
-        pk10t = E.pack_conv(w10.detach().transpose(0, 1).flip(3, 4), None, None, (1, 1, 1), (0, 1, 1), E.ACT_NONE,
-                            prec=E.PREC_F32)
-        d8 = E.upsample_bwd(E.conv(d10, pk10t), 4, u=u, act=E.ACT_RELU)
+        d8 = E.upsample_bwd(E.conv(d10, _pack_dgrad(w10, (0, 1, 1))), 4, u=u, act=E.ACT_RELU)
         if need[1] or need[2]:
             dw8, db8 = E.conv_wgrad(x4, d8, pk8)
             grads[1], grads[2] = (dw8 if need[1] else None), (db8 if need[2] else None)
@@ -115,21 +171,43 @@ BN_EPS, BN_MOMENTUM = 1e-5, 0.1          # nn.BatchNorm3d's defaults, which the 
 
 
 def _bn_running(buffers, mean, var, M, momentum):
-    """The running-stat update of nn.BatchNorm3d.train(): the UNBIASED variance into running_var, num_batches_tracked += 1."""
+    """The running-stat update of nn.BatchNorm3d.train(): the UNBIASED variance into running_var, num_batches_tracked += 1
+    (buffers None: skipped)."""
+    if buffers is None:
+        return
     rm, rv, nbt = buffers
     rm.mul_(1.0 - momentum).add_(mean, alpha=momentum)
     rv.mul_(1.0 - momentum).add_(var, alpha=momentum * M / (M - 1.0))
     nbt.add_(1)
 
 
-def _bn_train(x, gamma, beta, buffers):
-    """BatchNorm on batch statistics + ReLU, and the running-stat update of nn.BatchNorm3d.train() with momentum 0.1 (buffers
-    None: skipped).  Returns (y, mean, rstd)."""
-    mean, var, rstd = E.bn_stats(x, BN_EPS)
-    y = E.bn_apply(x, mean, rstd, gamma.detach().contiguous(), beta.detach().contiguous(), act=E.ACT_RELU)
-    if buffers is not None:
-        _bn_running(buffers, mean, var, x.M, BN_MOMENTUM)
-    return y, mean, rstd
+BN_MAX_CH = 192                          # widest channel count the mspi_bn_* entry points take
+
+
+def _bn_slices(c):
+    """Channel slices the BatchNorm kernels take: the statistics are per channel, so a wider layer in slices is exact."""
+    if c <= BN_MAX_CH:
+        return [(0, c)]
+    n = -(-c // BN_MAX_CH)
+    step = (-(-c // n) + 3) // 4 * 4
+    return [(c0, min(step, c - c0)) for c0 in range(0, c, step)]
+
+
+def bn_relu_train(x, gamma, beta, eps, out=None):
+    """BatchNorm on the batch statistics of the CL x, then ReLU, into out (None: a new CL like x): bn_stats and bn_apply over
+    _bn_slices(x.C).  Returns (y, mean, biased var, rstd); where one slice covers the width the three are bn_stats' own vectors.
+    The running statistics are the caller's (_bn_running)."""
+    gamma, beta = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+    if out is None:
+        out = E.alloc(x.N, x.T, x.H, x.W, x.C, x.buf.device)
+    stats = []
+    for c0, c in _bn_slices(x.C):
+        xs = x.slice(c0, c)
+        mean, var, rstd = E.bn_stats(xs, eps)
+        E.bn_apply(xs, mean, rstd, gamma[c0:c0 + c], beta[c0:c0 + c], act=E.ACT_RELU, out=out.slice(c0, c))
+        stats.append((mean, var, rstd))
+    mean, var, rstd = stats[0] if len(stats) == 1 else (torch.cat(ts) for ts in zip(*stats))
+    return out, mean, var, rstd
 
 
 def _cl5(t):
@@ -152,8 +230,7 @@ class ReadoutHead(torch.autograd.Function):
     def forward(ctx, s0, s1, s2, s3, w0, b0, w1, b1, g2, be2, w4, b4, g5, be5, bn2, bn5):
         maps = []
         for j, s in enumerate((s0, s1, s2, s3)):
-            if not s.is_cuda:
-                raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % s.device)
+            _check_input(s)
             if s.dim() != 5 or s.dtype != torch.float32 or s.shape[4] != s0.shape[4] or s.shape[:2] != s0.shape[:2] or \
                     (s.shape[2] << j, s.shape[3] << j) != tuple(s0.shape[2:4]):
                 raise MspiError("ReadoutHead: s%d %s does not continue the pyramid of s0 %s (fp32 channels-last, each level "
@@ -167,12 +244,14 @@ class ReadoutHead(torch.autograd.Function):
             pk1 = E.pack_conv(w1, b1, None, (1, 1, 1), (1, 1, 1), E.ACT_NONE)
             pk4 = E.pack_conv(w4, b4, None, (1, 1, 1), (0, 1, 1), E.ACT_NONE)
             x1 = E.conv(y0, pk1)
-            a1, m2, r2 = _bn_train(x1, g2, be2, bn2)
+            a1, m2, v2, r2 = bn_relu_train(x1, g2, be2, BN_EPS)
+            _bn_running(bn2, m2, v2, x1.M, BN_MOMENTUM)
             x4 = E.conv(a1, pk4)
-            y4, m5, r5 = _bn_train(x4, g5, be5, bn5)
+            y4, m5, v5, r5 = bn_relu_train(x4, g5, be5, BN_EPS)
+            _bn_running(bn5, m5, v5, x4.M, BN_MOMENTUM)
         ctx.save_for_backward(*maps, y0.buf, x1.buf, a1.buf, x4.buf, y4.buf, m2, r2, m5, r5, w1, g2, w4, g5, w0, b0)
         ctx.packs = (parts, pk1, pk4)
-        return y4.buf.view(y4.N, y4.T, y4.H, y4.W, y4.ld)
+        return y4.as_nthwc()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -187,12 +266,9 @@ class ReadoutHead(torch.autograd.Function):
         y0, x1, a1, x4, y4 = cl(y0b, c1), cl(x1b, c1), cl(a1b, c1), cl(x4b, c4), cl(y4b, c4)
         d4, dg5, dbe5 = E.bn_bwd(cl(g.float().contiguous().view(-1), c4), x4, m5, r5, g5.detach().contiguous(), y=y4)
         dw4, db4 = E.conv_wgrad_wide(a1, d4, pk4)
-        # data gradient of a stride-1 "same" conv: the same conv with w'[ci][-tap][co], on the fp32 MFMA path (ReadoutTail.backward)
-        pk4t = E.pack_conv(w4.detach().transpose(0, 1).flip(3, 4), None, None, (1, 1, 1), (0, 1, 1), E.ACT_NONE, prec=E.PREC_F32)
-        d1, dg2, dbe2 = E.bn_bwd(E.conv(d4, pk4t), x1, m2, r2, g2.detach().contiguous(), y=a1)
+        d1, dg2, dbe2 = E.bn_bwd(E.conv(d4, _pack_dgrad(w4, (0, 1, 1))), x1, m2, r2, g2.detach().contiguous(), y=a1)
         dw1, db1 = E.conv_wgrad_wide(y0, d1, pk1)
-        pk1t = E.pack_conv(w1.detach().transpose(0, 1).flip(2, 3, 4), None, None, (1, 1, 1), (1, 1, 1), E.ACT_NONE, prec=E.PREC_F32)
-        dy0 = E.conv(d1, pk1t)
+        dy0 = E.conv(d1, _pack_dgrad(w1, (1, 1, 1)))
         # dW0 without the 768-channel concat: the adjoint of r0_parts.  y0 = W0 s0 + b + sum_j up_j((W0 + Wj) sj'), j = 1, 2, 3,
         # and <up_j(A s), dy0> = <A s, up_j^T dy0>, so with g_j = up_j^T dy0 (upsample_bwd) and G0 = dy0^T s0, G_j = g_j^T sj':
         #   dL/dW0 = G0 + G1 + G2 + G3 (W0 takes part in every term), dL/dWj = G_j, db0 = sum dy0
@@ -201,13 +277,8 @@ class ReadoutHead(torch.autograd.Function):
         Gs = [E.conv_wgrad_wide(_cl5(s), g, pk)[0] for s, g, pk in ((s1, gs[1], parts[1]), (s2, gs[2], parts[2]), (s3, gs[3], parts[3]))]
         dw0 = torch.cat([((G0 + Gs[0]) + Gs[1]) + Gs[2]] + Gs, dim=1)
         need = ctx.needs_input_grad
-        # the maps' gradients, each only when asked for: d s0 = W0^T dy0, d sj = (W0 + Wj)^T g_j -- the transposed 1x1x1 part on
-        # the fp32 MFMA path, its operand being a gradient at the loss's scale (ReadoutTail.backward)
-        dmaps = [None] * 4
-        for j, (wj, _) in enumerate(r0_parts(w0, b0)):
-            if need[j]:
-                d = E.conv(gs[j], E.pack_conv(wj.t().contiguous(), None, prec=E.PREC_F32))
-                dmaps[j] = d.buf.view(d.N, d.T, d.H, d.W, d.ld)
+        # the maps' gradients, each only when asked for: d s0 = W0^T dy0, d sj = (W0 + Wj)^T g_j
+        dmaps = [E.conv(gs[j], _pack_t(wj)).as_nthwc() if need[j] else None for j, (wj, _) in enumerate(r0_parts(w0, b0))]
         grads = dmaps + [dw0, db0, dw1, db1, dg2, dbe2, dw4, db4, dg5, dbe5, None, None]
         return tuple(gr if need[i] else None for i, gr in enumerate(grads))
 
@@ -244,8 +315,7 @@ class Fusion(torch.autograd.Function):
         sa, bns = [rest[5 * k:5 * k + 5] for k in range(3)], rest[15:]
         lats = []
         for j, t in enumerate((l0, l1, l2, l3)):
-            if not t.is_cuda:
-                raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % t.device)
+            _check_input(t)
             if t.dim() != 5 or t.dtype != torch.float32 or t.shape[4] != l0.shape[4] or t.shape[4] % 4 or t.shape[:2] != l0.shape[:2] or \
                     (t.shape[2] << j, t.shape[3] << j) != tuple(l0.shape[2:4]):
                 raise MspiError("Fusion: l%d %s does not continue the pyramid of l0 %s (fp32 channels-last, a multiple of 4 wide, "
@@ -267,11 +337,9 @@ class Fusion(torch.autograd.Function):
             pre = E.conv(x, E.pack_conv(torch.cat([p[0] for p in sa], 0), None, None, (1, 1, 1), (1, 1, 1), E.ACT_NONE))
             gamma = torch.cat([p[1].detach().float() for p in sa]).contiguous()
             beta = torch.cat([p[2].detach().float() for p in sa]).contiguous()
-            mean, var, rstd = E.bn_stats(pre, SA_BN_EPS)
-            pm = E.bn_apply(pre, mean, rstd, gamma, beta, act=E.ACT_RELU)
+            pm, mean, var, rstd = bn_relu_train(pre, gamma, beta, SA_BN_EPS)
             for k, bn in enumerate(bns):
-                if bn is not None:
-                    _bn_running(bn, mean[k * mid:(k + 1) * mid], var[k * mid:(k + 1) * mid], pre.M, SA_BN_MOMENTUM)
+                _bn_running(bn, mean[k * mid:(k + 1) * mid], var[k * mid:(k + 1) * mid], pre.M, SA_BN_MOMENTUM)
             outs, ms, gates = [], [], []
             for k in (2, 1, 0):                       # the order of _fuse_readout
                 m = pm.slice(k * mid, mid)
@@ -291,7 +359,7 @@ class Fusion(torch.autograd.Function):
         ctx.save_for_backward(lats[0], lats[1], lats[2], masks, pre.buf, pm.buf, mean, rstd, gamma, *ms[::-1], *gates[::-1],
                               *[p[3] for p in sa], *[p[0] for p in sa])
         ctx.dims = (B, T, h, w, D, Cm, mid)
-        return tuple(t.buf.view(t.N, t.T, t.H, t.W, t.ld) for t in (s0, s1, s2)) + (lats[3].clone(),)
+        return tuple(t.as_nthwc() for t in (s0, s1, s2)) + (lats[3].clone(),)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -307,11 +375,10 @@ class Fusion(torch.autograd.Function):
             return _cl5(torch.zeros(shape, dtype=torch.float32, device=dev) if g is None else g.float().contiguous())
         G = [grad(g, j) for j, g in enumerate((G0, G1, G2, G3))]
         # s2 = gate(l2) + up2(l3), s1 = gate(l1) + up2(s2) + up4(l3):  D2 = G2 + up2^T G1,  D3 = G3 + up4^T G1 + up2^T D2
-        D2 = E.upsample_sum_bwd(_cl5(G[2].buf.view(B, T, h >> 2, w >> 2, D).clone()), [(G[1], 2)], accumulate=True)
+        D2 = E.upsample_sum_bwd(_cl5(G[2].as_nthwc().clone()), [(G[1], 2)], accumulate=True)
         grads = [None] * 23
         if need[3]:
-            D3 = E.upsample_sum_bwd(_cl5(G[3].buf.view(B, T, h >> 3, w >> 3, D).clone()), [(G[1], 4), (D2, 2)], accumulate=True)
-            grads[3] = D3.buf.view(B, T, h >> 3, w >> 3, D)
+            grads[3] = E.upsample_sum_bwd(_cl5(G[3].as_nthwc().clone()), [(G[1], 4), (D2, 2)], accumulate=True).as_nthwc()
         sa_need = any(need[4:20])                # the gradient of masks runs through the three gates as well
         dp = E.alloc(B, T, hm, wm, 3 * mid, dev)
         for k, (Gk, lk, mb, gb, w2) in enumerate(((G[0], l0, m0b, g0b, w20), (G[1], l1, m1b, g1b, w21), (D2, l2, m2b, g2b, w22))):
@@ -321,7 +388,7 @@ class Fusion(torch.autograd.Function):
             hk, wk = h >> k, w >> k
             dl, dz = E.rowgate_bwd(Gk, _cl5(lk), E.CL(gb, 0, B, T, hk, wk, 1, 1), need_dx=need[k])
             if need[k]:
-                grads[k] = dl.buf.view(B, T, hk, wk, D)
+                grads[k] = dl.as_nthwc()
             if not sa_need:
                 continue
             # mspi_conv_c1_bwd masks its data gradient where its input y <= 0, and that is exact for all three gates.  sa_2
@@ -340,24 +407,10 @@ class Fusion(torch.autograd.Function):
             return tuple(grads)
         pre, pm = E.CL(preb, 0, B, T, hm, wm, 3 * mid, 3 * mid), E.CL(pmb, 0, B, T, hm, wm, 3 * mid, 3 * mid)
         dpre, dgam, dbet = E.bn_bwd(dp, pre, mean, rstd, gamma, y=pm)
-        # the (3,3,3) conv's weight gradient in input-channel slices the wide kernel takes (512 = 192 + 192 + 128): a slice of
-        # the wider tensor as it stands where the kernel accepts its strides, a dense copy where it refuses
-        x = _cl5(masks)
-        parts = []
-        for c0 in range(0, Cm, WGRAD_WIDE_MAX_CH):
-            c = min(WGRAD_WIDE_MAX_CH, Cm - c0)
-            xs, geo = x.slice(c0, c), _geometry((3, 3, 3), (1, 1, 1), c, 3 * mid)
-            if E.conv_wgrad_wide_variant(xs, dpre, geo) < 0:
-                xs = _cl5(masks[..., c0:c0 + c].contiguous())
-            parts.append(E.conv_wgrad_wide(xs, dpre, geo)[0])
-        dW = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
-        if need[4]:
-            # data gradient of the concatenated (3,3,3) conv Cm -> 3 mid: the same conv with w'[ci][-tap][co], on the fp32 MFMA
-            # path (ReadoutHead.backward)
-            wcat = torch.cat([wc0.detach(), wc1.detach(), wc2.detach()], 0)
-            pkt = E.pack_conv(wcat.transpose(0, 1).flip(2, 3, 4), None, None, (1, 1, 1), (1, 1, 1), E.ACT_NONE, prec=E.PREC_F32)
-            dm = E.conv(dpre, pkt)
-            grads[4] = dm.buf.view(B, T, hm, wm, dm.ld)
+        # the (3,3,3) conv's weight gradient in input-channel slices the wide kernel takes (512 = 192 + 192 + 128)
+        dW = wgrad_wide_sliced(_cl5(masks), dpre, (3, 3, 3), (1, 1, 1))[0]
+        if need[4]:      # the data gradient of the concatenated (3,3,3) conv Cm -> 3 mid
+            grads[4] = E.conv(dpre, _pack_dgrad(torch.cat([wc0, wc1, wc2], 0), (1, 1, 1))).as_nthwc()
         for k in range(3):
             sl = slice(k * mid, (k + 1) * mid)
             grads[5 + 5 * k], grads[5 + 5 * k + 1], grads[5 + 5 * k + 2] = dW[sl], dgam[sl], dbet[sl]
@@ -390,25 +443,33 @@ def convnext_block_forward(x, pk, out=None):
     return E.conv(E.conv(E.layernorm(b, *pk["ln"], LN_EPS), pk["p1"]), pk["p2"], res=x, out=out), a, b
 
 
-def _wide_slices(x, dy, over_input):
-    """Weight and bias gradient of a 1x1x1 conv wider than mspi_conv_wgrad_wide_fwd takes, in slices of at most
-    WGRAD_WIDE_MAX_CH channels of x (over_input) or of dy: a slice of the wider tensor as it stands where the kernel accepts
-    its strides, a dense copy where it refuses (Fusion.backward).  Returns (dW [Co,Ci,1,1,1], db [Co])."""
-    wide = x if over_input else dy
+def _wide_cut(c):
+    """Even channel slices of at most WGRAD_WIDE_MAX_CH, multiples of 32: 512 -> 192, 192, 128; 416 -> 160, 160, 96."""
+    n = -(-c // WGRAD_WIDE_MAX_CH)
+    step = -(-c // n // 32) * 32
+    return [(c0, min(step, c - c0)) for c0 in range(0, c, step)]
+
+
+def wgrad_wide_sliced(x, dy, k, pad):
+    """Weight and bias gradient of a stride-1 conv from mspi_conv_wgrad_wide_fwd where both widths are multiples of 32, in
+    slices (_wide_cut) of the channels of x, of dy or of both: a slice of the wider tensor as it stands where the kernel accepts
+    its strides, a dense copy where it refuses; an operand one slice covers is the tensor itself and is never copied.  Returns
+    (dW [Co,Ci,kt,kh,kw], db [Co]); every output slice's db comes with its first input slice."""
+    def part(t, c0, c, dense):
+        if c == t.C:
+            return t
+        return E.from_rows(t.as_rows()[:, c0:c0 + c].contiguous()).reshape(t.N, t.T, t.H, t.W) if dense else t.slice(c0, c)
     dWs, dbs = [], []
-    for c0 in range(0, wide.C, WGRAD_WIDE_MAX_CH):
-        c = min(WGRAD_WIDE_MAX_CH, wide.C - c0)
-        xs, ds = (wide.slice(c0, c), dy) if over_input else (x, wide.slice(c0, c))
-        geo = _geometry((1, 1, 1), (0, 0, 0), xs.C, ds.C)
-        if E.conv_wgrad_wide_variant(xs, ds, geo) < 0:
-            dense = E.from_rows(wide.as_rows()[:, c0:c0 + c].contiguous()).reshape(wide.N, wide.T, wide.H, wide.W)
-            xs, ds = (dense, dy) if over_input else (x, dense)
-        dW, db = E.conv_wgrad_wide(xs, ds, geo)
-        dWs.append(dW)
-        dbs.append(db)
-    if len(dWs) == 1:
-        return dWs[0], dbs[0]
-    return (torch.cat(dWs, 1), dbs[0]) if over_input else (torch.cat(dWs, 0), torch.cat(dbs, 0))
+    for o0, oc in _wide_cut(dy.C):
+        cols = []
+        for c0, cc in _wide_cut(x.C):
+            xs, ds, geo = part(x, c0, cc, False), part(dy, o0, oc, False), _geometry(k, pad, cc, oc)
+            if E.conv_wgrad_wide_variant(xs, ds, geo) < 0:
+                xs, ds = part(x, c0, cc, True), part(dy, o0, oc, True)
+            cols.append(E.conv_wgrad_wide(xs, ds, geo))
+        dWs.append(cols[0][0] if len(cols) == 1 else torch.cat([dW for dW, _ in cols], 1))
+        dbs.append(cols[0][1])
+    return (dWs[0], dbs[0]) if len(dWs) == 1 else (torch.cat(dWs, 0), torch.cat(dbs, 0))
 
 
 class LateralBlock(torch.autograd.Function):
@@ -422,10 +483,7 @@ class LateralBlock(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wt, bt, ws, bs, gamma, beta, w1, b1, w2, b2):
-        if not x.is_cuda:
-            raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % x.device)
-        if x.dim() != 5 or x.dtype != torch.float32:
-            raise MspiError("LateralBlock: x must be fp32 [B,T,h,w,D] (channels-last), got %s %s" % (x.dtype, tuple(x.shape)))
+        _check_input(x, "LateralBlock: x", "[B,T,h,w,D]")
         D = x.shape[4]
         if D % 32:
             raise MspiError("LateralBlock: D = %d is not a multiple of 32 (D %% 32 != 0)" % D)
@@ -442,7 +500,7 @@ class LateralBlock(torch.autograd.Function):
             y, a, b = convnext_block_forward(_cl5(x), pk)
         ctx.save_for_backward(x, a.buf, b.buf, wt, ws, gamma, beta, w1, b1, w2)
         ctx.packs = (pk["dt"], pk["ds"])
-        return y.buf.view(y.N, y.T, y.H, y.W, y.ld)
+        return y.as_nthwc()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -459,12 +517,11 @@ class LateralBlock(torch.autograd.Function):
         # the recompute works on activations, so the forward's f16x3 pack serves; the GELU is taken apart from it (z is needed)
         n = E.layernorm(b, gam, beta.detach().float().contiguous(), LN_EPS)
         z = E.conv(n, E.pack_conv(w1, b1))                                   # [M, 4D]
-        # the two data-gradient GEMMs on the fp32 MFMA path: their operand is a gradient (ReadoutTail.backward)
-        dg = E.conv(Gc, E.pack_conv(w2.detach().flatten(1).t().contiguous(), None, prec=E.PREC_F32))
+        dg = E.conv(Gc, _pack_t(w2))
         g, dz = E.gelu_bwd(z, dg, inplace=True)                              # g over z, dz over dg
-        dw2, db2 = _wide_slices(g, Gc, over_input=True)
-        dw1, db1 = _wide_slices(n, dz, over_input=False)
-        dn = E.conv(dz, E.pack_conv(w1.detach().flatten(1).t().contiguous(), None, prec=E.PREC_F32))
+        dw2, db2 = wgrad_wide_sliced(g, Gc, (1, 1, 1), (0, 0, 0))            # the 4D-wide side in slices: x here, dy below
+        dw1, db1 = wgrad_wide_sliced(n, dz, (1, 1, 1), (0, 0, 0))
+        dn = E.conv(dz, _pack_t(w1))
         db_, dgamma, dbeta = E.layernorm_bwd(dn, b, gam, LN_EPS)
         # padding 3 under kernel 7 is symmetric: the adjoint of a depthwise conv is the same conv on the flipped taps, no bias
         da = E.dwconv(db_, E.pack_dwconv(ws.detach().flip(2, 3, 4), None, None, (1, 1, 1), (0, 3, 3)))
@@ -474,7 +531,7 @@ class LateralBlock(torch.autograd.Function):
         if need[0]:
             dx = E.dwconv(da, E.pack_dwconv(wt.detach().flip(2, 3, 4), None, None, (1, 1, 1), (3, 0, 0)))
             E.add(dx.buf, Gc.buf, dx.buf)                                                # the residual
-            dx = dx.buf.view(B, T, h, w, D)
+            dx = dx.as_nthwc()
         grads = (dx, dwt, dbt, dws, dbs, dgamma, dbeta, dw1, db1, dw2, db2)
         return tuple(gr if need[i] else None for i, gr in enumerate(grads))
 
@@ -506,8 +563,7 @@ def pack_lateral_entry(w0, b0, w1, stride, split=None):
 def _cl_view(name, t):
     """A CL over the tensor t [B,T,h,w,C] as it lies in memory: frames, lines and positions nested (a channel slice of a wider
     buffer keeps its row stride), any sample stride (a token view into a slab)."""
-    if t.dim() != 5 or t.dtype != torch.float32:
-        raise MspiError("LateralEntry: %s must be fp32 [B,T,h,w,C] (channels-last), got %s %s" % (name, t.dtype, tuple(t.shape)))
+    _check_input(t, "LateralEntry: %s" % name)
     B, T, h, w, c = t.shape
     sN, sT, sH, sW, sC = t.stride()
     if sC != 1 or sW % 4 or sW < c or sH != w * sW or sT != h * sH or sN % 4 or t.data_ptr() % 16:
@@ -531,8 +587,7 @@ class LateralEntry(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x2, w0, b0, w1):
-        if not x.is_cuda or (x2 is not None and x2.device != x.device):
-            raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % x.device)
+        _check_input(x, beside=x2)
         xc = _cl_view("x", x.detach())
         xc2 = None if x2 is None else _cl_view("x2", x2.detach())
         cin = xc.C + (xc2.C if xc2 is not None else 0)
@@ -560,7 +615,7 @@ class LateralEntry(torch.autograd.Function):
         ctx.dims = [(v.N, v.T, v.H, v.W, v.C, v.ld, v.sN) for v in views]
         ctx.has1 = w1 is not None
         ctx.geoms = [_geometry((s, 1, 1), (0, 0, 0), p.cin, p.cout_s, (s, 1, 1)) for p in pks]
-        return y.buf.view(y.N, y.T, y.H, y.W, y.ld)
+        return y.as_nthwc()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -610,39 +665,6 @@ class LateralEntry(torch.autograd.Function):
 ADAPTER_LAYERS = ("b0", "b1a", "b1s", "b1t", "b2a", "b2s", "b2t", "b3")      # branch0 | branch1: 1x1x1, conv_s, conv_t | branch2 | branch3
 _ADAPTER_KERNEL = {"s": ((1, 3, 3), (0, 1, 1)), "t": ((3, 1, 1), (1, 0, 0))}
 _ADAPTER_CHAINS = (("b0",), ("b1a", "b1s", "b1t"), ("b2a", "b2s", "b2t"), ("b3",))
-BN_MAX_CH = 192                          # widest channel count the mspi_bn_* entry points take
-
-
-def _bn_slices(c):
-    """Channel slices the BatchNorm kernels take: the statistics are per channel, so a wider layer in slices is exact."""
-    if c <= BN_MAX_CH:
-        return [(0, c)]
-    n = -(-c // BN_MAX_CH)
-    step = (-(-c // n) + 3) // 4 * 4
-    return [(c0, min(step, c - c0)) for c0 in range(0, c, step)]
-
-
-def wgrad_wide_sliced(x, dy, k, pad):
-    """The weight gradient of a stride-1 conv from mspi_conv_wgrad_wide_fwd where both widths are multiples of 32: slices of at
-    most WGRAD_WIDE_MAX_CH channels of either, even ones, a slice of the wider tensor as it stands where the kernel accepts its
-    strides and a dense copy where it refuses (_wide_slices).  Returns dW [Co,Ci,kt,kh,kw]."""
-    def cut(c):
-        n = -(-c // WGRAD_WIDE_MAX_CH)
-        step = -(-c // n // 32) * 32
-        return [(c0, min(step, c - c0)) for c0 in range(0, c, step)]
-
-    def dense(t, c0, c):
-        return E.from_rows(t.as_rows()[:, c0:c0 + c].contiguous()).reshape(t.N, t.T, t.H, t.W)
-    rows = []
-    for o0, oc in cut(dy.C):
-        cols = []
-        for c0, cc in cut(x.C):
-            xs, ds, geo = x.slice(c0, cc), dy.slice(o0, oc), _geometry(k, pad, cc, oc)
-            if E.conv_wgrad_wide_variant(xs, ds, geo) < 0:
-                xs, ds = dense(x, c0, cc), dense(dy, o0, oc)
-            cols.append(E.conv_wgrad_wide(xs, ds, geo)[0])
-        rows.append(cols[0] if len(cols) == 1 else torch.cat(cols, 1))
-    return rows[0] if len(rows) == 1 else torch.cat(rows, 0)
 
 
 def adapter_wgrad_route(rows, cin, cout):
@@ -659,7 +681,7 @@ def adapter_wgrad_route(rows, cin, cout):
 def adapter_wgrad(x, dz, geo):
     """The weight gradient of one adapter layer (no bias), by the route adapter_wgrad_route names."""
     if adapter_wgrad_route(x.M, geo.cin, geo.cout) == "wide":
-        return wgrad_wide_sliced(x, dz, geo.k, geo.pad)
+        return wgrad_wide_sliced(x, dz, geo.k, geo.pad)[0]
     return E.conv_wgrad_t16(x, dz, geo)[0]
 
 
@@ -680,10 +702,7 @@ class Adapter(torch.autograd.Function):
     def forward(ctx, cat, *rest):
         if len(rest) != 32:
             raise MspiError("Adapter: expected 24 tensors and 8 BatchNorm buffer triples after cat, got %d arguments" % len(rest))
-        if not cat.is_cuda:
-            raise MspiError("mspi_amd runs on the GPU only (tensor on %s); there is no CPU fallback" % cat.device)
-        if cat.dim() != 5 or cat.dtype != torch.float32:
-            raise MspiError("Adapter: cat must be fp32 [B,T,h,w,C] (channels-last), got %s %s" % (cat.dtype, tuple(cat.shape)))
+        _check_input(cat, "Adapter: cat")
         ps = {l: rest[3 * i:3 * i + 3] for i, l in enumerate(ADAPTER_LAYERS)}
         bns = dict(zip(ADAPTER_LAYERS, rest[24:]))
         B, T, h, w, cin = cat.shape
@@ -716,22 +735,15 @@ class Adapter(torch.autograd.Function):
                     x = (pooled if l == "b3" else x0) if src[l] is None else ys[src[l]]
                     z = E.conv(x, E.pack_conv(ps[l][0], None, None, (1, 1, 1), pad, E.ACT_NONE))
                     y = out.slice(c0, co) if l == chain[-1] else E.alloc(B, T, h, w, co, cat.device)
-                    gam, bet = ps[l][1].detach().float().contiguous(), ps[l][2].detach().float().contiguous()
-                    mean, var, rstd = (torch.empty(co, dtype=torch.float32, device=cat.device) for _ in range(3))
-                    for s0, sc in _bn_slices(co):
-                        m_, v_, r_ = E.bn_stats(z.slice(s0, sc), SA_BN_EPS)
-                        E.bn_apply(z.slice(s0, sc), m_, r_, gam[s0:s0 + sc].contiguous(), bet[s0:s0 + sc].contiguous(), act=E.ACT_RELU,
-                                   out=y.slice(s0, sc))
-                        mean[s0:s0 + sc], var[s0:s0 + sc], rstd[s0:s0 + sc] = m_, v_, r_
-                    if bns[l] is not None:
-                        _bn_running(bns[l], mean, var, z.M, SA_BN_MOMENTUM)
-                    ys[l], stats[l] = y, (z.buf, mean, rstd, gam)
+                    _, mean, var, rstd = bn_relu_train(z, ps[l][1], ps[l][2], SA_BN_EPS, out=y)
+                    _bn_running(bns[l], mean, var, z.M, SA_BN_MOMENTUM)
+                    ys[l], stats[l] = y, (z.buf, mean, rstd, ps[l][1].detach().float().contiguous())
                 c0 += cw
         for l in ADAPTER_LAYERS:
             saved += [stats[l][0], ys[l].buf, stats[l][1], stats[l][2], stats[l][3], ps[l][0]]
         ctx.save_for_backward(*saved, pooled.buf)
         ctx.dims, ctx.geos, ctx.widths = (B, T, h, w), geos, widths
-        return out.buf.view(B, T, h, w, out.ld)
+        return out.as_nthwc()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -775,9 +787,6 @@ class Adapter(torch.autograd.Function):
                 grads[1 + 3 * i] = adapter_wgrad(x, dz, _geometry(k, pad, c, co)).contiguous()
                 grads[2 + 3 * i], grads[3 + 3 * i] = dgam, dbet
                 if j:
-                    # data gradient of a stride-1 "same" conv: the same conv with w'[ci][-tap][co], on the fp32 MFMA path
-                    # (ReadoutTail.backward)
-                    dy = E.conv(dz, E.pack_conv(wl.detach().transpose(0, 1).flip(2, 3, 4), None, None, (1, 1, 1), pad, E.ACT_NONE,
-                                                prec=E.PREC_F32))
+                    dy = E.conv(dz, _pack_dgrad(wl, pad))
             c0 += cw
         return tuple(g if g is None or need[i] else None for i, g in enumerate(grads))

@@ -274,6 +274,12 @@ class CL:
         return self.buf.as_strided((self.N, c, T, H, W), (self.sN, 1, H * W * ld, W * ld, ld),
                                    self.buf.storage_offset() + self.off)
 
+    def as_nthwc(self):
+        """Logical [N,T,H,W,C] view (no copy) -- what the autograd Functions take and return."""
+        ld, H, W = self.ld, self.H, self.W
+        return self.buf.as_strided((self.N, self.T, H, W, self.C), (self.sN, H * W * ld, W * ld, ld, 1),
+                                   self.buf.storage_offset() + self.off)
+
     def as_rows(self, channels=None):
         c = self.C if channels is None else channels
         assert self.dense

@@ -21,8 +21,9 @@ import torch.nn as nn
 from .. import engine as E
 from .._lib import MspiError
 from ..autograd import Adapter as AdapterTrain
-from ..autograd import (Fusion, LateralBlock, LateralEntry, ReadoutHead, ReadoutTail, compose_lateral, convnext_block_forward,
-                        pack_convnext_block, pack_lateral_entry, pack_readout_tail, r0_parts, readout_tail_forward)
+from ..autograd import (STAGE_NAMES, STAGES, Fusion, LateralBlock, LateralEntry, ReadoutHead, ReadoutTail, compose_lateral,
+                        convnext_block_forward, pack_convnext_block, pack_lateral_entry, pack_readout_tail, r0_parts, reaches,
+                        readout_tail_forward, stage_rank, stages_upto)
 from ..backbones.convnext import ConvNeXtTinyFeatures
 from ..backbones.resnet import get_resnet18
 from ..module import HipModule, to_cl
@@ -178,6 +179,11 @@ class SA(HipModule):
             nn.Sigmoid(),
         )
 
+    def tensors(self):
+        """The five tensors in the order of autograd.Fusion's arguments and the BatchNorm buffer triple behind them."""
+        b, c = self.conv_mask[0], self.conv_mask[2]
+        return [b.conv.weight, b.bn.weight, b.bn.bias, c.weight, c.bias], (b.bn.running_mean, b.bn.running_var, b.bn.num_batches_tracked)
+
     def _pack(self):
         c = self.conv_mask[2]
         return self.conv_mask[0].packed(), E.pack_conv(c.weight, c.bias, None, (1, 1, 1), (0, 1, 1), E.ACT_SIGMOID)
@@ -244,8 +250,8 @@ class Adapter(HipModule):
                 "conv.branch2.1.bn_t": (b2[1].conv_t, b2[1].bn_t), "conv.branch3.1.bn": (c.branch3[1].conv, c.branch3[1].bn)}
 
     def run(self, o3, o2, features=False):
-        """o3 CL [(b t),1,h,w,96], o2 CL [(b t),1,h/2,w/2,320] -> masks CL [B,T/stride,h,w,512]; features == "cat" stops in
-        front of the Inception and returns its 416-wide input for autograd.Adapter."""
+        """o3 CL [(b t),1,h,w,96], o2 CL [(b t),1,h/2,w/2,320] -> masks CL [B,T/stride,h,w,512]; features at the "adapter" stage
+        stops in front of the Inception and returns its 416-wide input for autograd.Adapter."""
         T, s = self.num_frames, self.stride
         B = o3.N // T
         o3 = o3.reshape(B, T, o3.H, o3.W)
@@ -253,7 +259,7 @@ class Adapter(HipModule):
         cat = E.alloc(B, T // s, o3.H, o3.W, o3.C + o2.C, o3.buf.device)
         E.maxpool(o3, (s, 1, 1), (s, 1, 1), (0, 0, 0), out=cat.slice(0, o3.C))
         E.upsample(E.maxpool(o2, (s, 1, 1), (s, 1, 1), (0, 0, 0)), 2, dst=cat.slice(o3.C, o2.C))
-        return cat if features == "cat" else self.conv.run(cat)
+        return cat if reaches(features, "adapter") else self.conv.run(cat)
 
 
 class LayerNorm3d(nn.Module):
@@ -458,15 +464,15 @@ class _SaliencyBase(HipModule):
         return [E.pack_conv(w, b) for w, b in self._r0_parts(conv.weight, conv.bias)]
 
     def _lateral(self, pk, k, xs, out=None, features=False):
-        """latlayer_k: the entry conv(s), then the ConvNextBlock -- left to autograd.LateralBlock when features == "entries";
-        features == "inputs" stops in front of the entry conv(s) and returns the encoder map(s) for autograd.LateralEntry, split
-        planes joined into fp32 rows."""
-        if features in ("inputs", "cat"):
+        """latlayer_k: the entry conv(s), then the ConvNextBlock -- left to autograd.LateralBlock from the "lateral_blocks" stage
+        on; from "lateral_entries" on it stops in front of the entry conv(s) and returns the encoder map(s) for
+        autograd.LateralEntry, split planes joined into fp32 rows."""
+        if reaches(features, "lateral_entries"):
             return [E.join_planes(x) if isinstance(x, E.SP) else x for x in xs]
         y = E.conv(xs[0], pk["lat"][k][0])
         if len(xs) == 2:
             y = E.conv(xs[1], pk["lat"][k][1], res=y)
-        if features == "entries":
+        if reaches(features, "lateral_blocks"):
             return y
         return getattr(self, "latlayer_%d" % k)[-1].run(y, out=out)
 
@@ -511,13 +517,13 @@ class _SaliencyBase(HipModule):
         and returns y4 [B,4,h,w,64]; "maps" stops in front of readout[0]; "laterals" in front of the gating (pm is None then);
         "entries" likewise, s0..s3 then being the entry convs' outputs (_lateral); "inputs" likewise, s0..s3 being the lists of
         encoder maps the entry convs read."""
-        if features in ("laterals", "entries", "inputs", "cat"):
+        if reaches(features, "fusion"):
             # trainable("adapter"): as "inputs", and masks is the Inception's input, for autograd.Adapter;
             # trainable("fusion"): autograd.Fusion takes over from here, then ReadoutHead; trainable("lateral_blocks"): s0..s3
             # are the entry convs' outputs, and autograd.LateralBlock comes first; trainable("lateral_entries"): the entry
             # convs' inputs, and autograd.LateralEntry comes before that
             return s0, s1, s2, s3, masks
-        if features != "maps":         # "maps": ReadoutHead packs the live values itself
+        if not reaches(features, "readout"):      # "maps": ReadoutHead packs the live values itself
             self._refresh_head(pk)
         self.sa_2.run(s2, masks, pm.slice(64, 32))
         E.upsample(s3, 2, dst=s2, accumulate=True)
@@ -526,7 +532,7 @@ class _SaliencyBase(HipModule):
             # r0 on the coarse maps, up-sampled after it (_r0_parts): neither s0' nor the 768-channel concat is materialised
             E.upsample_sum(s1, [(s2, 2), (s3, 4)])
             self.sa_0.run(s0, masks, pm.slice(0, 32))
-            if features == "maps":     # trainable("readout"): autograd.ReadoutHead takes over from here
+            if reaches(features, "readout"):      # trainable("readout"): autograd.ReadoutHead takes over from here
                 return s0, s1, s2, s3
             p0, p1, p2, p3 = pk["r0_parts"]
             y = E.conv(s0, p0)
@@ -589,9 +595,9 @@ class _SaliencyBase(HipModule):
             self.__dict__.pop("_pk", None)
             return
         with torch.no_grad():
-            if grad_tail not in ("laterals", "entries", "inputs", "cat"):    # ... autograd.Fusion for the SA fold, whose premask that forward does not launch
+            if not reaches(grad_tail, "fusion"):       # ... autograd.Fusion for the SA fold, whose premask that forward does not launch
                 self._refresh_sa(pk)
-            if grad_tail not in ("maps", "laterals", "entries", "inputs", "cat"):
+            if not reaches(grad_tail, "readout"):
                 self._refresh_head(pk)
             if not grad_tail:          # ... and ReadoutTail does the same for the tail
                 self._refresh_tail(pk)
@@ -620,7 +626,7 @@ class _SaliencyBase(HipModule):
             ts += [b.conv.weight, b.bn.weight, b.bn.bias, b.bn.running_mean, b.bn.running_var]
         return tuple((t.data_ptr(), t._version) for t in ts)
 
-    TAIL_PARAMS = tuple("readout.%d.%s" % (i, n) for i in (8, 10, 12) for n in ("weight", "bias"))
+    TAIL_PARAMS = STAGES[0].params
 
     def trainable(self, what):
         """trainable("adapter"): on top of what "lateral_entries" trains, the adapter's Inception -- the eight conv -> BatchNorm3d
@@ -659,40 +665,23 @@ class _SaliencyBase(HipModule):
                 p.requires_grad_(flag)
             d["_trainable"] = None
             return self
-        if what not in ("readout_tail", "readout", "fusion", "lateral_blocks", "lateral_entries", "adapter"):
-            raise MspiError("trainable: %r is not a trainable part of this model (only 'readout_tail', 'readout', 'fusion', "
-                            "'lateral_blocks', 'lateral_entries' and 'adapter' are)" % (what,))
-        if what in ("readout", "fusion", "lateral_blocks", "lateral_entries", "adapter") and not DECODER_FUSED:
+        if what not in STAGE_NAMES:
+            raise MspiError("trainable: %r is not a trainable part of this model (only %s and %r are)"
+                            % (what, ", ".join(repr(n) for n in STAGE_NAMES[:-1]), STAGE_NAMES[-1]))
+        if reaches(what, "readout") and not DECODER_FUSED:
             raise MspiError("trainable(%r) needs the fused decoder path: it is switched off by MSPI_DECODER_FUSED=0" % (what,))
         if d.get("_trainable") is None:
             d["_trainable_saved"] = [(p, p.requires_grad) for p in self.parameters()]
         d["_trainable"] = what
-        tail = set(self.TAIL_PARAMS)
-        blocks = tuple("latlayer_%d.%d." % (k, len(getattr(self, "latlayer_%d" % k)) - 1) for k in range(4))
+        prefixes = tuple(p.format(k=k, last=len(getattr(self, "latlayer_%d" % k)) - 1)
+                         for st in stages_upto(what) for p in st.params for k in range(4))
         for name, p in self.named_parameters():
-            if what == "adapter":              # ... and the adapter's Inception
-                p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.", "latlayer_", "adapter.")))
-            elif what == "lateral_entries":    # every tensor of the four laterals
-                p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.", "latlayer_")))
-            elif what == "lateral_blocks":
-                p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.") + blocks))
-            elif what == "fusion":
-                p.requires_grad_(name.startswith(("readout.", "sa_0.", "sa_1.", "sa_2.")))
-            else:
-                p.requires_grad_(name.startswith("readout.") if what == "readout" else name in tail)
+            p.requires_grad_(name.startswith(prefixes))
         return self
 
     def _batch_stat_modules(self):
         """{name: module} of the BatchNorm layers that run on batch statistics under the present switch."""
-        what = self.__dict__.get("_trainable")
-        mods = {}
-        if what in ("readout", "fusion", "lateral_blocks", "lateral_entries", "adapter"):
-            mods.update({"readout.2": self.readout[2], "readout.5": self.readout[5]})
-        if what in ("fusion", "lateral_blocks", "lateral_entries", "adapter"):   # LayerNorm has no mode, convs neither: the laterals add nothing
-            mods.update({"sa_%d.conv_mask.0.bn" % k: getattr(self, "sa_%d" % k).conv_mask[0].bn for k in range(3)})
-        if what == "adapter":              # the Inception's eight
-            mods.update({"adapter.%s" % n: bn for n, (_, bn) in self.adapter.layers().items()})
-        return mods
+        return {n: self.get_submodule(n) for st in stages_upto(self.__dict__.get("_trainable")) for n in st.batch_stat}
 
     def _training_tail(self):
         """What _forward stops at when this forward carries a graph: True (the features y4, for autograd.ReadoutTail), "maps"
@@ -702,10 +691,7 @@ class _SaliencyBase(HipModule):
         autograd.LateralEntry in front of those four), "cat" (the same with the Inception's input in the place of the masks, for
         autograd.Adapter beside those) or False."""
         what = self.__dict__.get("_trainable")
-        if what is None or not torch.is_grad_enabled():
-            return False
-        return {"readout": "maps", "fusion": "laterals", "lateral_blocks": "entries", "lateral_entries": "inputs",
-                "adapter": "cat"}.get(what, True)
+        return STAGES[stage_rank(what)].stop if what is not None and torch.is_grad_enabled() else False
 
     def _check_eval(self):
         """The forward's guard.  Under trainable("readout") exactly readout[2] and readout[5] may be in train() (they run on
@@ -713,28 +699,13 @@ class _SaliencyBase(HipModule):
         under trainable("lateral_blocks") and trainable("lateral_entries") the same five; any other module in train() is refused by name, as the model itself is."""
         super()._check_eval()
         what = self.__dict__.get("_trainable")
-        if what not in ("readout", "fusion", "lateral_blocks", "lateral_entries", "adapter"):
+        if not reaches(what, "readout"):
             return
         allowed = {id(m) for m in self._batch_stat_modules().values()}
         for name, mod in self.named_modules():
             if mod.training and id(mod) not in allowed:
-                if what == "readout":
-                    raise MspiError("%s.%s is in train() mode: under trainable('readout') only readout.2 and readout.5 run on "
-                                    "batch statistics; call frozen_encoder()" % (type(self).__name__, name))
-                if what == "lateral_blocks":
-                    raise MspiError("%s.%s is in train() mode: under trainable('lateral_blocks') only readout.2, readout.5 and "
-                                    "the three sa_k.conv_mask.0.bn run on batch statistics (the blocks' LayerNorm has no mode); "
-                                    "call frozen_encoder()" % (type(self).__name__, name))
-                if what == "adapter":
-                    raise MspiError("%s.%s is in train() mode: under trainable('adapter') only readout.2, readout.5, the three "
-                                    "sa_k.conv_mask.0.bn and the eight BatchNorm layers of adapter.conv run on batch statistics; "
-                                    "call frozen_encoder()" % (type(self).__name__, name))
-                if what == "lateral_entries":
-                    raise MspiError("%s.%s is in train() mode: under trainable('lateral_entries') only readout.2, readout.5 and "
-                                    "the three sa_k.conv_mask.0.bn run on batch statistics (neither the entry convs nor the "
-                                    "blocks' LayerNorm have a mode); call frozen_encoder()" % (type(self).__name__, name))
-                raise MspiError("%s.%s is in train() mode: under trainable('fusion') only readout.2, readout.5 and the three "
-                                "sa_k.conv_mask.0.bn run on batch statistics; call frozen_encoder()" % (type(self).__name__, name))
+                raise MspiError("%s.%s is in train() mode: under trainable('%s') %s; call frozen_encoder()"
+                                % (type(self).__name__, name, what, STAGES[stage_rank(what)].only))
 
     def _frozen_eval(self):
         """frozen_encoder() under a trainable switch: eval() everywhere (folded BatchNorm), except that the readout's two
@@ -747,57 +718,49 @@ class _SaliencyBase(HipModule):
             mod.train()
         return True
 
-    def _tail_with_grad(self, y4):
+    def _tail_with_grad(self, y):
+        """The rest of a forward that carries a graph, from what _forward stopped at (_training_tail) to the map: the stages'
+        autograd Functions on the live tensors, lowest part of the network first."""
+        what = self.__dict__.get("_trainable")
         r = self.readout
-        if isinstance(y4, tuple) and len(y4) == 5:
-            # trainable("fusion"): the lateral outputs and the masks; autograd.Fusion hands ReadoutHead maps that carry a graph
-            what = self.__dict__.get("_trainable")
+        if reaches(what, "fusion"):
             idle = [n for n, m in self._batch_stat_modules().items() if not m.training]
             if idle:
                 raise MspiError("trainable('%s'): a forward with grad runs %s on batch statistics, but in eval() mode the "
                                 "no_grad forward folds the running ones; call frozen_encoder() (engine_train.train_one_epoch does)"
                                 % (what, ", ".join(idle)))
-            if what in ("lateral_entries", "adapter"):
-                # the encoder maps: the entry convs run here, from the live tensors, and their outputs carry a graph
-                entries = []
-                for k, xs in enumerate(y4[:4]):
-                    seq = getattr(self, "latlayer_%d" % k)
-                    ts = [x.buf.as_strided((x.N, x.T, x.H, x.W, x.C), (x.sN, x.H * x.W * x.ld, x.W * x.ld, x.ld, 1),
-                                           x.buf.storage_offset() + x.off) for x in xs]
-                    entries.append(LateralEntry.apply(ts[0], ts[1] if len(ts) == 2 else None, seq[0].weight, seq[0].bias,
-                                                      seq[1].weight if len(seq) == 3 else None))
-                m = y4[4]
-                y4 = [LateralBlock.apply(t, *getattr(self, "latlayer_%d" % k)[-1].tensors()) for k, t in enumerate(entries)]
-                m = m.buf.view(m.N, m.T, m.H, m.W, m.ld)
-                if what == "adapter":
-                    # the Inception's input: its eight layers run here, from the live tensors, and the masks carry a graph
-                    ts, bns = self.adapter.tensors()
-                    m = AdapterTrain.apply(m, *ts, *bns)
-                y4.append(m)
-            elif what == "lateral_blocks":
-                # the entry convs' outputs: the four ConvNextBlocks run here, from the live tensors, and carry a graph
-                tensors = [s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4]
-                y4 = [LateralBlock.apply(t, *getattr(self, "latlayer_%d" % k)[-1].tensors()) for k, t in enumerate(tensors[:4])]
-                y4.append(tensors[4])
-            sa, bns = [], []
-            for m in (self.sa_0, self.sa_1, self.sa_2):
-                b, c = m.conv_mask[0], m.conv_mask[2]
-                sa += [b.conv.weight, b.bn.weight, b.bn.bias, c.weight, c.bias]
-                bns.append((b.bn.running_mean, b.bn.running_var, b.bn.num_batches_tracked))
-            y4 = Fusion.apply(*[s if torch.is_tensor(s) else s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4], *sa, *bns)
-        if isinstance(y4, tuple):
+            lats, m = list(y[:4]), y[4].as_nthwc()
+            seqs = [getattr(self, "latlayer_%d" % k) for k in range(4)]
+            if reaches(what, "lateral_entries"):      # the encoder maps: the entry convs run here and their outputs carry a graph
+                lats = [LateralEntry.apply(xs[0].as_nthwc(), xs[1].as_nthwc() if len(xs) == 2 else None, seq[0].weight, seq[0].bias,
+                                           seq[1].weight if len(seq) == 3 else None) for xs, seq in zip(lats, seqs)]
+            else:
+                lats = [s.as_nthwc() for s in lats]
+            if reaches(what, "lateral_blocks"):       # the entry convs' outputs: the four ConvNextBlocks
+                lats = [LateralBlock.apply(t, *seq[-1].tensors()) for t, seq in zip(lats, seqs)]
+            if reaches(what, "adapter"):              # the Inception's input: its eight layers, and the masks carry a graph
+                ts, bns = self.adapter.tensors()
+                m = AdapterTrain.apply(m, *ts, *bns)
+            sa, bns = zip(*[g.tensors() for g in (self.sa_0, self.sa_1, self.sa_2)])
+            y = Fusion.apply(*lats, m, *sum(sa, []), *bns)      # hands ReadoutHead maps that carry a graph
+        if reaches(what, "readout"):
             if not (r[2].training and r[5].training):
                 # ReadoutHead normalises with BATCH statistics whatever the modules' mode; in eval() the no_grad forward of the
                 # same model folds the RUNNING statistics, so the two maps would differ silently
                 raise MspiError("trainable('readout'): a forward with grad runs readout.2 and readout.5 on batch statistics, "
                                 "but they are in eval() mode; call frozen_encoder() (engine_train.train_one_epoch does)")
-            bn = [(r[i].running_mean, r[i].running_var, r[i].num_batches_tracked) for i in (2, 5)]
-            maps = [s if torch.is_tensor(s) else s.buf.view(s.N, s.T, s.H, s.W, s.ld) for s in y4]
-            y = ReadoutHead.apply(*maps, r[0].weight, r[0].bias, r[1].weight, r[1].bias, r[2].weight, r[2].bias, r[4].weight,
-                                  r[4].bias, r[5].weight, r[5].bias, bn[0], bn[1])
-            return ReadoutTail.apply(y, r[8].weight, r[8].bias, r[10].weight, r[10].bias, r[12].weight, r[12].bias)
-        y = y4.buf.view(y4.N, y4.T, y4.H, y4.W, y4.ld)
-        return ReadoutTail.apply(y, r[8].weight, r[8].bias, r[10].weight, r[10].bias, r[12].weight, r[12].bias)
+            ts, bns = self._head_tensors()
+            y = ReadoutHead.apply(*[s if torch.is_tensor(s) else s.as_nthwc() for s in y], *ts, *bns)
+        else:
+            y = y.as_nthwc()
+        return ReadoutTail.apply(y, *[self.get_parameter(n) for n in self.TAIL_PARAMS])
+
+    def _head_tensors(self):
+        """The ten tensors of readout[0], [1], [2], [4], [5] in the order of autograd.ReadoutHead's arguments and the two BatchNorm
+        buffer triples behind them."""
+        r = self.readout
+        return ([t for i in (0, 1, 2, 4, 5) for t in (r[i].weight, r[i].bias)],
+                [(r[i].running_mean, r[i].running_var, r[i].num_batches_tracked) for i in (2, 5)])
 
     def _try_load(self, module_loader, path, what):
         if os.path.exists(path):
@@ -905,7 +868,7 @@ class AudioVisualSaliencyModel(_SaliencyBase):
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
                 masks = self.adapter.run(o1, o0, features)   # "cat": the Inception's input, for autograd.Adapter
-                pm = None if features in ("laterals", "entries", "inputs", "cat") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
+                pm = None if reaches(features, "fusion") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             with fk.branch(1):
                 aud = self.audnet.forward_cl(audios.float())
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
@@ -973,7 +936,7 @@ class VisualSaliencyModel(_SaliencyBase):
             with fk.branch(0):
                 o1, o0 = self.image_encoder.run(clips) if frame_feats is None else self._wrap_frame_feats(frame_feats)
                 masks = self.adapter.run(o1, o0, features)   # "cat": the Inception's input, for autograd.Adapter
-                pm = None if features in ("laterals", "entries", "inputs", "cat") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
+                pm = None if reaches(features, "fusion") else self._premask(pk, masks)    # autograd.Fusion runs its own, unfolded
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
             cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3, features)
             s3 = self._lateral(pk, 3, [v4], features=features)

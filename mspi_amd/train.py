@@ -31,12 +31,13 @@ import os
 import torch
 
 from ._lib import MspiError
+from .autograd import STAGE_NAMES
 
-TRAINABLE = ("readout_tail", "readout")           # what trains on a frozen pyramid
-TRAINABLE_STAGES = TRAINABLE + ("fusion",)        # ... and on frozen laterals
-TRAINABLE_BLOCKS = ("lateral_blocks",)            # ... and with the laterals' ConvNextBlocks
-TRAINABLE_ENTRIES = ("lateral_entries",)          # ... and with the laterals' entry convs
-TRAINABLE_ADAPTER = ("adapter",)                  # ... and with the adapter's Inception: every value --trainable takes
+TRAINABLE = STAGE_NAMES[:2]                       # what trains on a frozen pyramid
+TRAINABLE_STAGES = STAGE_NAMES[:3]                # ... and on frozen laterals
+TRAINABLE_BLOCKS = STAGE_NAMES[3:4]               # ... and with the laterals' ConvNextBlocks
+TRAINABLE_ENTRIES = STAGE_NAMES[4:5]              # ... and with the laterals' entry convs
+TRAINABLE_ADAPTER = STAGE_NAMES[5:]               # ... and with the adapter's Inception: every value --trainable takes
 
 
 def lr_by_epoch(cfg):
@@ -57,7 +58,7 @@ def _single_rank():
 
 
 def check_trainable(value):
-    if value not in TRAINABLE_STAGES + TRAINABLE_BLOCKS + TRAINABLE_ENTRIES + TRAINABLE_ADAPTER:
+    if value not in STAGE_NAMES:
         raise MspiError("--trainable %s: only %s can be trained on a frozen pyramid, and %s on frozen laterals, and %s on frozen "
                         "entry convs, and %s on a frozen adapter, and %s on frozen encoders (the models' backward stops behind the "
                         "laterals' entry convs and the adapter's Inception: the SyncBlock, the contrastive projectors and the "
@@ -69,7 +70,7 @@ def check_trainable(value):
 
 def build_parser():
     parser = argparse.ArgumentParser(prog="python -m mspi_amd.train", description=__doc__.split("\n")[0])
-    parser.add_argument("--trainable", default="readout_tail", type=str, help="the part of the model that trains: readout_tail, readout, fusion, lateral_blocks, lateral_entries or adapter")
+    parser.add_argument("--trainable", default="readout_tail", type=str, help="the part of the model that trains: %s or %s" % (", ".join(STAGE_NAMES[:-1]), STAGE_NAMES[-1]))
     parser.add_argument("--start_epoch", default=0, type=int)
     parser.add_argument("--split", default=1, type=int)
     parser.add_argument("--dataset", default="AVAD", type=str)
@@ -94,9 +95,8 @@ def train(model, data, cfg, device, log_dir, start_epoch=0, save_ckpt_freq=10, g
     from .metrics import SalLoss
     params = [p for p in model.parameters() if p.requires_grad]
     if not params:
-        raise MspiError("train: no parameter requires grad; call model.trainable('readout_tail'), model.trainable('readout'), "
-                        "model.trainable('fusion'), model.trainable('lateral_blocks'), model.trainable('lateral_entries') or "
-                        "model.trainable('adapter') first")
+        calls = ["model.trainable('%s')" % n for n in STAGE_NAMES]
+        raise MspiError("train: no parameter requires grad; call %s or %s first" % (", ".join(calls[:-1]), calls[-1]))
     optimizer = torch.optim.AdamW(params, cfg.SOLVER.LR, weight_decay=0)
     schedule = lr_by_epoch(cfg)
     ckpt_dir = os.path.join(log_dir, "checkpoints")

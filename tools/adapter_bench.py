@@ -43,7 +43,7 @@ def older_route(E, A, x, dy, k, pad):
         x = F.pad(x, (0, 32 - C % 32))
     if Co % 32:
         dy = F.pad(dy, (0, 32 - Co % 32))
-    return A.wgrad_wide_sliced(A._cl5(x), A._cl5(dy), k, pad)[:Co, :C]
+    return A.wgrad_wide_sliced(A._cl5(x), A._cl5(dy), k, pad)[0][:Co, :C]
 
 
 def kernel_alone(E, A, AR, dev, B, H, W, reps, rounds):

@@ -74,7 +74,7 @@ def kernel_alone(E, A, dev, B, H, W, reps, rounds):
                                                            [False, True, True])
 
             def older():      # a dense copy of each tap's frames, then the wide kernel on <= 192-channel slices
-                return [A._wide_slices(A._cl5(x[:, t::s].contiguous()), Gc, over_input=True) for t in range(s)]
+                return [A.wgrad_wide_sliced(A._cl5(x[:, t::s].contiguous()), Gc, (1, 1, 1), (0, 0, 0)) for t in range(s)]
             paths = {"entry": new, "torch": torch_bwd}
             if c % 32 == 0:
                 paths["copy_wide"] = older
