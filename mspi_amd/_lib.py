@@ -315,6 +315,18 @@ _ADAPTER_SIGNATURES = {
 
 ADAPTER_EXPORTS = tuple(_ADAPTER_SIGNATURES)
 
+# The transformer Block's backward declared in include/mspi_sync_train_hip.h (csrc/sync_bwd.hip): a sixth table, likewise
+_SYNC_SIGNATURES = {
+    "mspi_attn_bwd_ws_bytes": (C.c_size_t, [C.POINTER(AttnDesc)]),
+    "mspi_attn_bwd_variant": (C.c_int, [C.POINTER(AttnDesc)]),
+    "mspi_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mspi_layernorm_bwd_wide_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "mspi_layernorm_bwd_wide": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32,
+                                          _P]),
+}
+
+SYNC_EXPORTS = tuple(_SYNC_SIGNATURES)
+
 _lib = None
 
 
@@ -334,7 +346,7 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
-            list(_ENTRY_SIGNATURES.items()) + list(_ADAPTER_SIGNATURES.items()):
+            list(_ENTRY_SIGNATURES.items()) + list(_ADAPTER_SIGNATURES.items()) + list(_SYNC_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -17,7 +17,10 @@ block's ten tensors.  Its output is one of Fusion's laterals.
 
 LateralEntry: the entry conv(s) in front of that block -- latlayer_k[0], 1x1x1 C_k -> 192 with bias, and where present
 latlayer_k[1], (s,1,1) / stride (s,1,1) 192 -> 192 without bias, run composed as one conv (compose_lateral) -- over the
-encoder map(s).  Its output is LateralBlock's input, whose gradient LateralBlock computes when it is asked for."""
+encoder map(s).  Its output is LateralBlock's input, whose gradient LateralBlock computes when it is asked for.
+
+TransformerBlock: one pre-LN transformer Block of the SyncBlock (model/model_utils.py:84-152) over its input tokens and its
+eleven tensors.  No stage of the ladder reaches it yet: the embedding in front of the blocks and the stage itself come next."""
 import collections
 
 import torch
@@ -533,6 +536,108 @@ class LateralBlock(torch.autograd.Function):
             E.add(dx.buf, Gc.buf, dx.buf)                                                # the residual
             dx = dx.as_nthwc()
         grads = (dx, dwt, dbt, dws, dbs, dgamma, dbeta, dw1, db1, dw2, db2)
+        return tuple(gr if need[i] else None for i, gr in enumerate(grads))
+
+
+# ------------------------------------------------------------------------------------------------ transformer Block (SyncBlock)
+BLOCK_DIM, BLOCK_HEAD_DIM = 512, 128     # the SyncBlock's width and the one head dim mspi_attn_bwd is instantiated for
+BLOCK_TENSORS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
+                 "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+
+
+def pack_transformer_block(n1w, n1b, wqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2):
+    """The plan of a transformer Block from its eleven tensors in their nn layouts (qkv has no bias): the dict Block._pack
+    builds, here from the live values for TransformerBlock.forward.  Block._pack does not call it yet: routing the inference
+    path's packs through it was taken out of the change that added this function (DESIGN.md section 7 says why)."""
+    def f(t):
+        return t.detach().float().contiguous()
+    return {"n1": (f(n1w), f(n1b)), "n2": (f(n2w), f(n2b)),
+            "qkv": E.pack_conv(wqkv, None), "proj": E.pack_conv(wproj, bproj),
+            "fc1": E.pack_conv(w1, b1, act=E.ACT_GELU), "fc2": E.pack_conv(w2, b2)}
+
+
+def transformer_block_forward(x, pk, B, R, heads, scale):
+    """Block.run's launches on the plan pk, keeping what Block.run drops: (y, qkv, o, x1) with o the attention output and
+    x1 = x + proj(o), which the backward reads."""
+    dim = x.C
+    h = E.layernorm_for_gemm(x, *pk["n1"], LN_EPS, pk["qkv"])
+    qkv = E.conv(h, pk["qkv"])
+    o = E.attention(qkv, B, R, heads, dim // heads, scale, slot=E.attn_slot(pk))
+    x1 = E.conv(o, pk["proj"], res=x)
+    return E.mlp_tail(x1, ("split", pk["fc1"], pk["fc2"]), pk["n2"], LN_EPS, res=x1), qkv, o, x1
+
+
+class TransformerBlock(torch.autograd.Function):
+    """y = TransformerBlock.apply(x, n1w, n1b, wqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2): one pre-LN transformer Block on x,
+    fp32 [B,R,512] on the GPU -- norm1, attn.qkv (no bias), attn.proj, norm2, mlp.fc1 (512 -> 2048, GELU) and mlp.fc2 in their nn
+    layouts, 4 heads of 128.  The forward launches what Block.run launches, from packs of the parameters' present values
+    (pack_transformer_block, the dict of Block._pack), the attention's precision slot decided on this call's data as a freshly packed Block decides it, so
+    y has the bits of the inference path.  It keeps x, qkv, the attention output o and x1 = x + proj(o); the backward recomputes
+    the two LayerNorms and the 2048-wide z = W1 n + b1.  Attention backward and every data gradient run on the fp32 MFMA
+    (_pack_dgrad says why).  Gradients: the eleven tensors and x, each only when it requires grad.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, wqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2):
+        _check_input(x)
+        D, hd = BLOCK_DIM, BLOCK_HEAD_DIM
+        if x.dim() != 3 or x.dtype != torch.float32 or x.shape[2] != D:
+            raise MspiError("TransformerBlock: x must be fp32 [B,R,%d], got %s %s" % (D, x.dtype, tuple(x.shape)))
+        want = ((D,), (D,), (3 * D, D), (D, D), (D,), (D,), (D,), (4 * D, D), (4 * D,), (D, 4 * D), (D,))
+        for name, t, shape in zip(BLOCK_TENSORS, (n1w, n1b, wqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2), want):
+            if tuple(t.shape) != shape or t.device != x.device:
+                raise MspiError("TransformerBlock: %s is %s on %s, a Block of dim %d with heads of %d has %s on %s"
+                                % (name, tuple(t.shape), t.device, D, hd, shape, x.device))
+        x = x.detach().contiguous()
+        B, R, _ = x.shape
+        with torch.no_grad():
+            pk = pack_transformer_block(n1w, n1b, wqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2)
+            y, qkv, o, x1 = transformer_block_forward(E.CL(x.view(-1), 0, B, R, 1, 1, D, D), pk, B, R, D // hd, hd ** -0.5)
+        ctx.save_for_backward(x, qkv.buf, o.buf, x1.buf, n1w, n1b, wqkv, wproj, n2w, n2b, w1, b1, w2)
+        ctx.geom = (qkv.off, qkv.ld, o.off, o.ld, x1.off, x1.ld)
+        return y.as_rows().view(B, R, D)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        xb, qkvb, ob, x1b, n1w, n1b, wqkv, wproj, n2w, n2b, w1, b1, w2 = ctx.saved_tensors
+        B, R, D = xb.shape
+        hd = BLOCK_HEAD_DIM
+        need = ctx.needs_input_grad
+        qoff, qld, ooff, old, xoff, xld = ctx.geom
+
+        def cl(buf, c, off=0, ld=None):
+            return E.CL(buf.view(-1), off, B, R, 1, 1, c, c if ld is None else ld)
+
+        def f(t):
+            return t.detach().float().contiguous()
+
+        def lin(dW):
+            return dW.flatten(1)
+        x, qkv, o, x1, Gc = cl(xb, D), cl(qkvb, 3 * D, qoff, qld), cl(ob, D, ooff, old), cl(x1b, D, xoff, xld), cl(G.float().contiguous(), D)
+        g1, g2 = f(n1w), f(n2w)
+        one = (1, 1, 1), (0, 0, 0)
+        # the recompute works on activations, so the forward's f16x3 pack serves; the GELU is taken apart from it (z is needed)
+        n = E.layernorm(x1, g2, f(n2b), LN_EPS)
+        z = E.conv(n, E.pack_conv(w1, b1))                                   # [M, 2048]
+        dg = E.conv(Gc, _pack_t(w2))
+        g, dz = E.gelu_bwd(z, dg, inplace=True)                              # g over z, dz over dg
+        dw2, db2 = wgrad_wide_sliced(g, Gc, *one)
+        dw1, db1 = wgrad_wide_sliced(n, dz, *one)
+        dn = E.conv(dz, _pack_t(w1))
+        dx1, dg2, dbt2 = E.layernorm_bwd_wide(dn, x1, g2, LN_EPS)
+        E.add(dx1.buf, Gc.buf, dx1.buf)                                      # the MLP's residual
+        dwp, dbp = wgrad_wide_sliced(o, dx1, *one)
+        do = E.conv(dx1, _pack_t(wproj))
+        dqkv = E.attention_bwd(qkv, o, do, B, R, D // hd, hd, hd ** -0.5)
+        h = E.layernorm(x, g1, f(n1b), LN_EPS)
+        dwq, _ = wgrad_wide_sliced(h, dqkv, *one)
+        dx = dg1 = dbt1 = None
+        if need[0] or need[1] or need[2]:
+            dh = E.conv(dqkv, _pack_t(wqkv))
+            dxc, dg1, dbt1 = E.layernorm_bwd_wide(dh, x, g1, LN_EPS)
+            E.add(dxc.buf, dx1.buf, dxc.buf)                                 # the attention's residual
+            dx = dxc.as_rows().view(B, R, D)
+        grads = (dx, dg1, dbt1, lin(dwq), lin(dwp), dbp, dg2, dbt2, lin(dw1), db1, lin(dw2), db2)
         return tuple(gr if need[i] else None for i, gr in enumerate(grads))
 
 

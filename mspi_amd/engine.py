@@ -27,7 +27,7 @@ __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedC
            "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "conv_wgrad_wide",
            "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "rowgate_bwd", "upsample_sum_bwd", "gelu_bwd",
            "layernorm_bwd", "dwconv_wgrad", "conv_wgrad_entry", "conv_wgrad_entry_variant", "conv_wgrad_t16",
-           "conv_wgrad_t16_variant", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "conv_wgrad_t16_variant", "attention_bwd", "layernorm_bwd_wide", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 # ----------------------------------------------------------------------------- conv autotuning
@@ -1439,6 +1439,69 @@ def conv_wgrad_t16(x, dy, pk, bias=False):
         check(lib.mspi_conv_wgrad_t16(C.byref(d), x.ptr, dy.ptr, dW.data_ptr(), db.data_ptr() if bias else None, ws.data_ptr(),
                                       _stream()), "mspi_conv_wgrad_t16")
     return dW.permute(0, 4, 1, 2, 3), db
+
+
+# ----------------------------------------------------------------------------- transformer Block backward (csrc/sync_bwd.hip)
+ATTN_BWD_PAIRS = ((128, 128),)           # the (D, Dv) pairs mspi_attn_bwd is instantiated for
+LN_BWD_WIDE_CH = (260, 512)              # the row widths mspi_layernorm_bwd_wide takes; below them mspi_layernorm_bwd
+
+
+def attention_bwd(qkv, o, dO, B, Ntok, heads, hd, scale, out=None):
+    """Backward of o = attention(qkv, B, Ntok, heads, hd, scale) for the output gradient dO: returns dqkv, a CL like qkv with
+    columns [3][heads][hd] = [dq | dk | dv].  o and dO are CLs of heads * hd columns with the rows of qkv.  out: the CL to write
+    (a slab like qkv; not qkv itself).  fp32 MFMA whatever the forward ran on: dO is a gradient (autograd._pack_dgrad)."""
+    lib = _lib.load()
+    for t in (qkv, o, dO) + ((out,) if out is not None else ()):
+        _need_gpu(t.buf)
+    Cc = heads * hd
+    if (hd, hd) not in ATTN_BWD_PAIRS:
+        raise MspiError("attention_bwd: head dim (D=%d, Dv=%d) not in %s" % (hd, hd, list(ATTN_BWD_PAIRS)))
+    if qkv.C != 3 * Cc or qkv.M != B * Ntok:
+        raise MspiError("attention_bwd: qkv is %d rows x %d columns, expected %d x %d ([3][%d][%d])" % (qkv.M, qkv.C, B * Ntok, 3 * Cc, heads, hd))
+    for name, t in (("o", o), ("dO", dO)):
+        if t.M != qkv.M or t.C != Cc or t.buf.device != qkv.buf.device:
+            raise MspiError("attention_bwd: %s is %d rows x %d columns on %s, expected %d x %d on %s"
+                            % (name, t.M, t.C, t.buf.device, qkv.M, Cc, qkv.buf.device))
+    if out is None:
+        out = alloc(qkv.N, qkv.T, qkv.H, qkv.W, 3 * Cc, qkv.buf.device)
+    elif out.M != qkv.M or out.C != 3 * Cc or out.buf.device != qkv.buf.device:
+        raise MspiError("attention_bwd: out is %d rows x %d columns on %s, expected %d x %d on %s"
+                        % (out.M, out.C, out.buf.device, qkv.M, 3 * Cc, qkv.buf.device))
+    d = AttnDesc()
+    d.B, d.Hh, d.Nq, d.Nk, d.D, d.Dv, d.nmask, d.nwin = B, heads, Ntok, Ntok, hd, hd, 0, 0
+    d.q_sB = d.k_sB = d.v_sB = Ntok * qkv.ld
+    d.q_sH = d.k_sH = d.v_sH = hd
+    d.q_sT = d.k_sT = d.v_sT = qkv.ld
+    d.o_sB, d.o_sH, d.o_sT = Ntok * o.ld, hd, o.ld
+    d.scale, d.prec = float(scale), PREC_F32
+    if out.ld != qkv.ld or dO.ld != o.ld:
+        raise MspiError("attention_bwd: out must have the row stride of qkv (%d, got %d) and dO that of o (%d, got %d)"
+                        % (qkv.ld, out.ld, o.ld, dO.ld))
+    ws = torch.empty(lib.mspi_attn_bwd_ws_bytes(C.byref(d)) // 4, dtype=torch.float32, device=qkv.buf.device)      # stream-ordered
+    with _Timed("attention_bwd", 14.0 * B * heads * Ntok * Ntok * hd, 4.0 * B * Ntok * Cc * 8, "B=%d h=%d N=%d d=%d" % (B, heads, Ntok, hd)):
+        check(lib.mspi_attn_bwd(C.byref(d), qkv.ptr, qkv.ptr + 4 * Cc, qkv.ptr + 8 * Cc, o.ptr, dO.ptr, out.ptr, out.ptr + 4 * Cc,
+                                out.ptr + 8 * Cc, ws.data_ptr(), _stream()), "mspi_attn_bwd")
+    return out
+
+
+def layernorm_bwd_wide(dy, x, gamma, eps=1e-5):
+    """layernorm_bwd for rows of 256 < C <= 512 channels (mspi_layernorm_bwd_wide): returns (dx, dgamma, dbeta), a CL like x and
+    two fp32 [C]."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    M, Cc = _bn_rows("layernorm_bwd_wide", x)
+    if not LN_BWD_WIDE_CH[0] <= Cc <= LN_BWD_WIDE_CH[1]:
+        raise MspiError("layernorm_bwd_wide: rows of %d channels, takes %d to %d (layernorm_bwd below)" % ((Cc,) + LN_BWD_WIDE_CH))
+    _rows_like("layernorm_bwd_wide", "dy", dy, x)
+    dev = x.buf.device
+    gp = _bn_vec("layernorm_bwd_wide", "gamma", gamma, Cc, dev)
+    dx = alloc(x.N, x.T, x.H, x.W, x.C, dev)
+    dgb = torch.empty(2, Cc, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_layernorm_bwd_wide_ws_bytes(M, Cc) // 4, dtype=torch.float32, device=dev)     # stream-ordered
+    with _Timed("layernorm_bwd_wide", 20.0 * M * Cc, 12.0 * M * Cc, "M=%d C=%d" % (M, Cc)):
+        check(lib.mspi_layernorm_bwd_wide(x.ptr, x.ld, dy.ptr, dy.ld, gp, float(eps), dx.ptr, dx.ld, dgb[0].data_ptr(),
+                                          dgb[1].data_ptr(), ws.data_ptr(), M, Cc, _stream()), "mspi_layernorm_bwd_wide")
+    return dx, dgb[0], dgb[1]
 
 
 def mean_rows(x, N, R, out):

@@ -88,6 +88,12 @@ class Block(HipModule):
         x = E.conv(o, pk["proj"], res=x)
         return E.mlp_tail(x, ("split", pk["fc1"], pk["fc2"]), pk["n2"], 1e-5, res=x)
 
+    def tensors(self):
+        """The eleven tensors in the order of autograd.TransformerBlock's arguments (and of pack_transformer_block's)."""
+        a, m = self.attn, self.mlp
+        return (self.norm1.weight, self.norm1.bias, a.qkv.weight, a.proj.weight, a.proj.bias, self.norm2.weight, self.norm2.bias,
+                m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias)
+
 
 class SyncBlock(HipModule):
     def __init__(self, num_blocks=3, num_vis_tokens=336, num_aud_tokens=36, vis_in_embed=1024, embed_dim=512):
