@@ -16,7 +16,8 @@
  * be initialised.  Non-finite data: PROPAGATE.
  *
  * What the Block's backward takes from elsewhere: mspi_gelu_bwd, the weight gradients of the four linear layers from
- * mspi_conv_wgrad_wide_fwd on channel slices, their data gradients from mspi_conv_fwd on transposed packs at MSPI_PREC_F32.
+ * mspi_linear_wgrad (mspi_linear_train_hip.h; one launch pair a layer, dqkv read in its slab), their data gradients from
+ * mspi_conv_fwd on transposed packs at MSPI_PREC_F32.
  */
 #ifndef MSPI_SYNC_TRAIN_HIP_H
 #define MSPI_SYNC_TRAIN_HIP_H

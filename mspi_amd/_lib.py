@@ -327,6 +327,15 @@ _SYNC_SIGNATURES = {
 
 SYNC_EXPORTS = tuple(_SYNC_SIGNATURES)
 
+# The linear layers' weight gradient declared in include/mspi_linear_train_hip.h (csrc/linear_wgrad.hip): a seventh table, likewise
+_LINEAR_SIGNATURES = {
+    "mspi_linear_wgrad_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "mspi_linear_wgrad_variant": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "mspi_linear_wgrad": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+}
+
+LINEAR_EXPORTS = tuple(_LINEAR_SIGNATURES)
+
 _lib = None
 
 
@@ -346,7 +355,7 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
-            list(_ENTRY_SIGNATURES.items()) + list(_ADAPTER_SIGNATURES.items()) + list(_SYNC_SIGNATURES.items()):
+            list(_ENTRY_SIGNATURES.items()) + list(_ADAPTER_SIGNATURES.items()) + list(_SYNC_SIGNATURES.items()) + list(_LINEAR_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

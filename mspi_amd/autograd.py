@@ -20,7 +20,9 @@ latlayer_k[1], (s,1,1) / stride (s,1,1) 192 -> 192 without bias, run composed as
 encoder map(s).  Its output is LateralBlock's input, whose gradient LateralBlock computes when it is asked for.
 
 TransformerBlock: one pre-LN transformer Block of the SyncBlock (model/model_utils.py:84-152) over its input tokens and its
-eleven tensors.  No stage of the ladder reaches it yet: the embedding in front of the blocks and the stage itself come next."""
+eleven tensors.  SyncEmbed: the embedding in front of the blocks (vis_proj, vis_norm, aud_norm, the sinusoid tables as
+constants); sync_block: the two chained, the whole SyncBlock over its 39 tensors.  No stage of the ladder reaches them yet: the
+stage itself comes next."""
 import collections
 
 import torch
@@ -567,6 +569,22 @@ def transformer_block_forward(x, pk, B, R, heads, scale):
     return E.mlp_tail(x1, ("split", pk["fc1"], pk["fc2"]), pk["n2"], LN_EPS, res=x1), qkv, o, x1
 
 
+def linear_wgrad_route(M, N, K):
+    """"linear" or "sliced": where TransformerBlock.backward takes the weight gradient of a linear layer of M rows, K -> N wide.
+    "linear" is one mspi_linear_wgrad launch pair on the operands as they lie; "sliced" is the path the Block had before,
+    wgrad_wide_sliced on <= 192-wide channel slices (99 launch pairs a Block).  tools/sync_block_bench.py times both in one
+    process by replacing this function; profiles/r22_sync_block.txt holds what was measured."""
+    return "linear"
+
+
+def block_linear_wgrad(x, dy, bias=True):
+    """(dW [N, K], db [N] or None) of a linear layer of the Block by the route linear_wgrad_route names."""
+    if linear_wgrad_route(x.M, dy.C, x.C) == "linear":
+        return E.linear_wgrad(x, dy, bias=bias)
+    dW, db = wgrad_wide_sliced(x, dy, (1, 1, 1), (0, 0, 0))
+    return dW.flatten(1), (db if bias else None)
+
+
 class TransformerBlock(torch.autograd.Function):
     """y = TransformerBlock.apply(x, n1w, n1b, wqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2): one pre-LN transformer Block on x,
     fp32 [B,R,512] on the GPU -- norm1, attn.qkv (no bias), attn.proj, norm2, mlp.fc1 (512 -> 2048, GELU) and mlp.fc2 in their nn
@@ -615,22 +633,21 @@ class TransformerBlock(torch.autograd.Function):
             return dW.flatten(1)
         x, qkv, o, x1, Gc = cl(xb, D), cl(qkvb, 3 * D, qoff, qld), cl(ob, D, ooff, old), cl(x1b, D, xoff, xld), cl(G.float().contiguous(), D)
         g1, g2 = f(n1w), f(n2w)
-        one = (1, 1, 1), (0, 0, 0)
         # the recompute works on activations, so the forward's f16x3 pack serves; the GELU is taken apart from it (z is needed)
         n = E.layernorm(x1, g2, f(n2b), LN_EPS)
         z = E.conv(n, E.pack_conv(w1, b1))                                   # [M, 2048]
         dg = E.conv(Gc, _pack_t(w2))
         g, dz = E.gelu_bwd(z, dg, inplace=True)                              # g over z, dz over dg
-        dw2, db2 = wgrad_wide_sliced(g, Gc, *one)
-        dw1, db1 = wgrad_wide_sliced(n, dz, *one)
+        dw2, db2 = block_linear_wgrad(g, Gc)
+        dw1, db1 = block_linear_wgrad(n, dz)
         dn = E.conv(dz, _pack_t(w1))
         dx1, dg2, dbt2 = E.layernorm_bwd_wide(dn, x1, g2, LN_EPS)
         E.add(dx1.buf, Gc.buf, dx1.buf)                                      # the MLP's residual
-        dwp, dbp = wgrad_wide_sliced(o, dx1, *one)
+        dwp, dbp = block_linear_wgrad(o, dx1)
         do = E.conv(dx1, _pack_t(wproj))
         dqkv = E.attention_bwd(qkv, o, do, B, R, D // hd, hd, hd ** -0.5)
         h = E.layernorm(x, g1, f(n1b), LN_EPS)
-        dwq, _ = wgrad_wide_sliced(h, dqkv, *one)
+        dwq, _ = block_linear_wgrad(h, dqkv, bias=False)                     # dqkv read in its slab
         dx = dg1 = dbt1 = None
         if need[0] or need[1] or need[2]:
             dh = E.conv(dqkv, _pack_t(wqkv))
@@ -639,6 +656,89 @@ class TransformerBlock(torch.autograd.Function):
             dx = dxc.as_rows().view(B, R, D)
         grads = (dx, dg1, dbt1, lin(dwq), lin(dwp), dbp, dg2, dbt2, lin(dw1), db1, lin(dw2), db2)
         return tuple(gr if need[i] else None for i, gr in enumerate(grads))
+
+
+SYNC_EMBED_TENSORS = ("vis_proj.weight", "vis_proj.bias", "vis_norm.weight", "vis_norm.bias", "aud_norm.weight", "aud_norm.bias")
+
+
+class SyncEmbed(torch.autograd.Function):
+    """slab = SyncEmbed.apply(vis, aud, wp, bp, gv, bv, ga, ba, vpos, apos): the embedding in front of the SyncBlock's transformer
+    blocks (model/model_utils.py:266-275 upstream) -- vis_norm(vis_proj(vis)) + vpos on the visual tokens, aud_norm(aud) + apos on
+    the audio tokens, concatenated along the tokens.  vis fp32 [B,t,h,w,C4] and aud [B,1,F,T',512], channels-last on the GPU;
+    wp [512,C4], bp, gv, bv, ga, ba [512] in their nn layouts; vpos [t h w, 512] and apos [F T', 512] the constant sinusoid tables
+    (no gradient).  The forward runs SyncBlock.run's three embedding launches from packs of the live values, so the slab
+    [B, Rv+Ra, 512] has the bits of the inference path.  It keeps vis, p = vis_proj(vis) and aud.  Backward, from the slab's
+    gradient: layernorm_bwd_wide on each row range (a dense copy of each), the projection's weight gradient from
+    engine.linear_wgrad and its data gradient on _pack_t at PREC_F32; each only when it is asked for.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, vis, aud, wp, bp, gv, bv, ga, ba, vpos, apos):
+        _check_input(vis, "SyncEmbed: vis", "[B,t,h,w,C4]", beside=aud)
+        _check_input(aud, "SyncEmbed: aud", "[B,1,F,T',512]")
+        D = BLOCK_DIM
+        B, t, h, w, C4 = vis.shape
+        if aud.shape[0] != B or aud.shape[4] != D:
+            raise MspiError("SyncEmbed: aud is %s, expected [%d,1,F,T',%d] beside vis %s" % (tuple(aud.shape), B, D, tuple(vis.shape)))
+        want = ((D, C4), (D,), (D,), (D,), (D,), (D,))
+        for name, p, shape in zip(SYNC_EMBED_TENSORS, (wp, bp, gv, bv, ga, ba), want):
+            if tuple(p.shape) != shape or p.device != vis.device:
+                raise MspiError("SyncEmbed: %s is %s on %s, the embedding of %d-wide visual tokens has %s on %s"
+                                % (name, tuple(p.shape), p.device, C4, shape, vis.device))
+        Rv, Ra = t * h * w, aud.shape[1] * aud.shape[2] * aud.shape[3]
+        if vpos.dim() != 2 or apos.dim() != 2 or Rv != vpos.shape[0] or Ra != apos.shape[0]:
+            raise MspiError("SyncBlock: got %d visual / %d audio tokens but the positional tables hold %d / %d rows "
+                            "-- set cfg.MODEL.NUM_VIS_TOKENS[name] / cfg.MODEL.NUM_AUD_TOKENS (reference: the add at "
+                            "model/model_utils.py:273-274 fails the same way)" % (Rv, Ra, vpos.shape[0], apos.shape[0]))
+
+        def f(p):
+            return p.detach().float().contiguous()
+        vis, aud = vis.detach().contiguous(), aud.detach().contiguous()
+        with torch.no_grad():
+            vc, ac = _cl5(vis), _cl5(aud)
+            x = E.alloc(B, Rv + Ra, 1, 1, D, vis.device)
+            p = E.conv(vc, E.pack_conv(wp, bp))
+            E.layernorm(p, f(gv), f(bv), LN_EPS, out=x.tokens(0, vc.T, vc.H, vc.W), table=f(vpos).to(vis.device))
+            E.layernorm(ac, f(ga), f(ba), LN_EPS, out=x.tokens(Rv, ac.T, ac.H, ac.W), table=f(apos).to(vis.device))
+        ctx.save_for_backward(vis, p.buf, aud, wp, gv, ga)
+        ctx.geom = (p.off, p.ld)
+        return x.as_rows().view(B, Rv + Ra, D)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        vis, pb, aud, wp, gv, ga = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        D = BLOCK_DIM
+        B, t, h, w, C4 = vis.shape
+        Rv, Ra = t * h * w, aud.shape[1] * aud.shape[2] * aud.shape[3]
+        poff, pld = ctx.geom
+        G = G.float()
+        dvis = daud = dwp = dbp = dgv = dbv = dga = dba = None
+        if any(need[i] for i in (0, 2, 3, 4, 5)):
+            dyv = E.from_rows(G[:, :Rv].reshape(B * Rv, D).contiguous())
+            p = E.CL(pb.view(-1), poff, B * Rv, 1, 1, 1, D, pld)
+            dp, dgv, dbv = E.layernorm_bwd_wide(dyv, p, gv.detach().float().contiguous(), LN_EPS)
+            if need[2] or need[3]:
+                dwp, dbp = E.linear_wgrad(E.from_rows(vis.view(B * Rv, C4)), dp)
+            if need[0]:
+                dvis = E.conv(dp, _pack_t(wp)).as_rows().view(B, t, h, w, C4)
+        if any(need[i] for i in (1, 6, 7)):
+            dya = E.from_rows(G[:, Rv:].reshape(B * Ra, D).contiguous())
+            da, dga, dba = E.layernorm_bwd_wide(dya, E.from_rows(aud.view(B * Ra, D)), ga.detach().float().contiguous(), LN_EPS)
+            daud = da.as_rows().view(aud.shape)
+        grads = (dvis, daud, dwp, dbp, dgv, dbv, dga, dba, None, None)
+        return tuple(gr if need[i] else None for i, gr in enumerate(grads))
+
+
+def sync_block(module, vis, aud):
+    """The SyncBlock `module` as a differentiable unit: SyncEmbed on (vis, aud) and module.tensors(), then TransformerBlock on
+    each of its blocks' tensors.  vis fp32 [B,t,h,w,C4] and aud [B,1,F,T',512], channels-last on the GPU.  Returns the slab
+    [B, Rv+Ra, 512], the bits of module.forward, with a graph over all 39 tensors (and vis and aud where they require grad)."""
+    dev = vis.device
+    x = SyncEmbed.apply(vis, aud, *module.tensors(), module.vis_pos_embed[0].to(dev), module.aud_pos_embed[0].to(dev))
+    for blk in module.blocks:
+        x = TransformerBlock.apply(x, *blk.tensors())
+    return x
 
 
 def compose_lateral(w0, b0, w1):

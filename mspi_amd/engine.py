@@ -27,7 +27,8 @@ __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedC
            "add", "fold_bn", "conv_wgrad", "conv_c1_bwd", "upsample_bwd", "logsumexp_sub_bwd", "conv_wgrad_wide",
            "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "rowgate_bwd", "upsample_sum_bwd", "gelu_bwd",
            "layernorm_bwd", "dwconv_wgrad", "conv_wgrad_entry", "conv_wgrad_entry_variant", "conv_wgrad_t16",
-           "conv_wgrad_t16_variant", "attention_bwd", "layernorm_bwd_wide", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "conv_wgrad_t16_variant", "attention_bwd", "layernorm_bwd_wide", "linear_wgrad",
+           "linear_wgrad_variant", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 # ----------------------------------------------------------------------------- conv autotuning
@@ -1502,6 +1503,43 @@ def layernorm_bwd_wide(dy, x, gamma, eps=1e-5):
         check(lib.mspi_layernorm_bwd_wide(x.ptr, x.ld, dy.ptr, dy.ld, gp, float(eps), dx.ptr, dx.ld, dgb[0].data_ptr(),
                                           dgb[1].data_ptr(), ws.data_ptr(), M, Cc, _stream()), "mspi_layernorm_bwd_wide")
     return dx, dgb[0], dgb[1]
+
+
+# ----------------------------------------------------------------------------- linear layers (csrc/linear_wgrad.hip)
+LINEAR_WGRAD_MAX_W = 4096                # widest N and K mspi_linear_wgrad takes
+LINEAR_WGRAD_WGS = 512                   # workgroups its slice arithmetic aims at (include/mspi_linear_train_hip.h)
+
+
+def linear_wgrad_variant(x, dy):
+    """Rows per slice of the launch linear_wgrad(x, dy) makes, -1 where it refuses; host only."""
+    return _lib.load().mspi_linear_wgrad_variant(x.ptr, x.ld, dy.ptr, dy.ld, x.M, dy.C, x.C)
+
+
+def linear_wgrad(x, dy, bias=True):
+    """Weight and bias gradient of y = x W^T + b over rows (mspi_linear_wgrad): x a CL of M rows x K columns, dy one of M rows x N
+    columns, each read where it lies (a channel slice of a wider buffer, the slab attention_bwd writes).  N a multiple of 32, K a
+    multiple of 4, both at most 4096.  Returns (dW [N, K], db [N] or None without bias)."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    _need_gpu(dy.buf)
+    if dy.buf.device != x.buf.device:
+        raise MspiError("linear_wgrad: x on %s, dy on %s" % (x.buf.device, dy.buf.device))
+    if dy.M != x.M:
+        raise MspiError("linear_wgrad: x has %d rows, dy %d: the row counts must match" % (x.M, dy.M))
+    if not x.dense or not dy.dense:
+        raise MspiError("linear_wgrad: x and dy must be rows one row stride apart (no sample stride of their own)")
+    M, N, K = x.M, dy.C, x.C
+    if lib.mspi_linear_wgrad_variant(x.ptr, x.ld, dy.ptr, dy.ld, M, N, K) < 0:
+        raise MspiError("linear_wgrad: %d rows, x %d wide (row stride %d), dy %d wide (row stride %d): %s"
+                        % (M, K, x.ld, N, dy.ld, lib.mspi_last_error().decode("utf-8", "replace")))
+    dev = x.buf.device
+    dW = torch.empty(N, K, dtype=torch.float32, device=dev)
+    db = torch.empty(N, dtype=torch.float32, device=dev) if bias else None
+    ws = torch.empty(lib.mspi_linear_wgrad_ws_bytes(M, N, K) // 4, dtype=torch.float32, device=dev)          # stream-ordered
+    with _Timed("linear_wgrad", 2.0 * M * N * K, 4.0 * M * (N + K), "M=%d K=%d N=%d" % (M, K, N)):
+        check(lib.mspi_linear_wgrad(x.ptr, x.ld, dy.ptr, dy.ld, dW.data_ptr(), db.data_ptr() if bias else None, ws.data_ptr(),
+                                    M, N, K, _stream()), "mspi_linear_wgrad")
+    return dW, db
 
 
 def mean_rows(x, N, R, out):

@@ -135,6 +135,11 @@ class SyncBlock(HipModule):
             x = blk.run(x, B, Rv + Ra)
         return x
 
+    def tensors(self):
+        """The six embedding tensors in the order of autograd.SyncEmbed's arguments (the blocks' are Block.tensors())."""
+        return (self.vis_proj.weight, self.vis_proj.bias, self.vis_norm.weight, self.vis_norm.bias, self.aud_norm.weight,
+                self.aud_norm.bias)
+
     def forward(self, vis_fea, aud_fea):
         a = aud_fea[:, :, None] if aud_fea.dim() == 4 else aud_fea
         x = self.run(to_cl(vis_fea), to_cl(a))
