@@ -336,6 +336,17 @@ _LINEAR_SIGNATURES = {
 
 LINEAR_EXPORTS = tuple(_LINEAR_SIGNATURES)
 
+# The contrastive head's backward declared in include/mspi_contrast_train_hip.h (csrc/contrast_bwd.hip): an eighth table, likewise
+_CONTRAST_SIGNATURES = {
+    "mspi_neg_cosine_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, _P]),
+    "mspi_layernorm_act_bwd_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "mspi_layernorm_act_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P, C.c_int64, _P, _P, _P, C.c_int64,
+                                         C.c_int32, _P]),
+    "mspi_mean_rows_bwd": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+}
+
+CONTRAST_EXPORTS = tuple(_CONTRAST_SIGNATURES)
+
 _lib = None
 
 
@@ -355,7 +366,8 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
-            list(_ENTRY_SIGNATURES.items()) + list(_ADAPTER_SIGNATURES.items()) + list(_SYNC_SIGNATURES.items()) + list(_LINEAR_SIGNATURES.items()):
+            list(_ENTRY_SIGNATURES.items()) + list(_ADAPTER_SIGNATURES.items()) + list(_SYNC_SIGNATURES.items()) + list(_LINEAR_SIGNATURES.items()) + \
+            list(_CONTRAST_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

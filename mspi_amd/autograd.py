@@ -21,8 +21,9 @@ encoder map(s).  Its output is LateralBlock's input, whose gradient LateralBlock
 
 TransformerBlock: one pre-LN transformer Block of the SyncBlock (model/model_utils.py:84-152) over its input tokens and its
 eleven tensors.  SyncEmbed: the embedding in front of the blocks (vis_proj, vis_norm, aud_norm, the sinusoid tables as
-constants); sync_block: the two chained, the whole SyncBlock over its 39 tensors.  No stage of the ladder reaches them yet: the
-stage itself comes next."""
+constants); sync_block: the two chained, the whole SyncBlock over its 39 tensors.  ContrastHead: the contrastive head behind it
+(the two pooled rows, projectors, predictors and the two negative cosines) over the slab and its 36 tensors.  No stage of the
+ladder holds them: trainable(what, sync=True) switches them on beside a stage that reaches "lateral_entries"."""
 import collections
 
 import torch
@@ -741,6 +742,142 @@ def sync_block(module, vis, aud):
     return x
 
 
+# ------------------------------------------------------------------------------------------------ contrastive head
+SYNC_PREFIXES = ("aud_vis_sync_block.", "vis_projector.", "mlp_vis.", "aud_projector.", "mlp_aud.")      # what sync=True adds
+CONTRAST_DIM, CONTRAST_HIDDEN = 512, 2048    # the slab's width (and the predictor's waist) and the projectors' width
+# one modality's 18 tensors in module order: projector [0] [1] [3] [4] [6] [7], predictor [0] [1] [3]; weight and bias each
+CONTRAST_TENSORS = tuple("%s.%d.%s" % (m, i, n) for m, idx in (("projector", (0, 1, 3, 4, 6, 7)), ("mlp", (0, 1, 3)))
+                         for i in idx for n in ("weight", "bias"))
+_CONTRAST_ACTS = (E.ACT_RELU, E.ACT_RELU, E.ACT_NONE, E.ACT_RELU)      # behind the four LayerNorms
+
+
+def pack_contrast_side(ts):
+    """The plan of one modality's projector and predictor from its 18 tensors (CONTRAST_TENSORS order): four (Linear pack,
+    LayerNorm weight, LayerNorm bias) and the last Linear's pack: the list AudioVisualSaliencyModel._pack holds as pk["vis"] /
+    pk["aud"], here from the live values for ContrastHead.forward.  _pack does not call it: the inference path's text is left as
+    it was (DESIGN.md section 7 says why), and tests/test_sync_train.py holds the two to the same bits."""
+    def f(t):
+        return t.detach().float().contiguous()
+    return [(E.pack_conv(ts[4 * i], ts[4 * i + 1]), f(ts[4 * i + 2]), f(ts[4 * i + 3])) for i in range(4)] + \
+        [E.pack_conv(ts[16], ts[17])]
+
+
+def contrast_embed_forward(p, x):
+    """projector (Linear-LN-ReLU x2, Linear-LN) then predictor (Linear-LN-ReLU, Linear) on the [B,512] rows x with the plan p
+    (pack_contrast_side): (emb, pred, zs, ys) -- the embedding, the prediction, the four Linear outputs in front of a LayerNorm
+    and the four rows behind them (ys[2] is emb), which the backward reads and inference drops."""
+    zs, ys = [], []
+    for i, act in enumerate(_CONTRAST_ACTS):
+        zs.append(E.conv(x, p[i][0]))
+        x = E.layernorm(zs[-1], p[i][1], p[i][2], LN_EPS, act=act)
+        ys.append(x)
+    return ys[2], E.conv(x, p[4]), zs, ys
+
+
+def contrast_forward(vis_fea, aud_fea, pv, pa):
+    """The launches of the contrastive side branch of AudioVisualSaliencyModel._sync_and_lateral3, restated, on the two token
+    views of the slab and the two plans: (loss [1], pooled [2,B,512], the two contrast_embed_forward results)."""
+    B, dev = vis_fea.N, vis_fea.buf.device
+    pooled = torch.empty(2, B, CONTRAST_DIM, dtype=torch.float32, device=dev)
+    E.mean_rows(vis_fea, B, vis_fea.T * vis_fea.H * vis_fea.W, pooled[0])
+    E.mean_rows(aud_fea, B, aud_fea.T * aud_fea.H * aud_fea.W, pooled[1])
+    vis = contrast_embed_forward(pv, E.from_rows(pooled[0]))
+    aud = contrast_embed_forward(pa, E.from_rows(pooled[1]))
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    E.neg_cosine(vis[1], aud[0], loss, 0.5, False)
+    E.neg_cosine(aud[1], vis[0], loss, 0.5, True)
+    return loss, pooled, vis, aud
+
+
+class ContrastHead(torch.autograd.Function):
+    """loss_av = ContrastHead.apply(slab, Rv, *36 tensors): the contrastive head (model/model_utils.py:545-552 upstream) on the
+    SyncBlock's slab, fp32 [B, Rv+Ra, 512] on the GPU, its first Rv rows the visual tokens: the mean over each modality's tokens,
+    projector and predictor, and 0.5 mean -cos(p_vis, z_aud) + 0.5 mean -cos(p_aud, z_vis), 0-dim.  The tensors: vis_projector,
+    mlp_vis, aud_projector, mlp_aud, each in module order (CONTRAST_TENSORS).  The forward restates the contrastive launches of
+    AudioVisualSaliencyModel._sync_and_lateral3 (contrast_forward) from packs of the live values (pack_contrast_side); the
+    value has the bits of the inference path's second return.  It keeps the two pooled rows, every Linear output in front of a
+    LayerNorm and the rows behind them.  The embeddings enter the loss only as the detached z (upstream's D(p, z.detach())), so
+    the gradient flows through the two predictions alone.  Backward per modality: neg_cosine_bwd; through predictor and
+    projector E.linear_wgrad for the five Linears, E.conv on _pack_t at PREC_F32 for their data gradients and
+    layernorm_act_bwd for the four LayerNorms (three under the ReLU's mask); mean_rows_bwd into that modality's row range of one
+    dslab.  Each gradient only when it is asked for.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, slab, Rv, *ts):
+        _check_input(slab)
+        D, Hd = CONTRAST_DIM, CONTRAST_HIDDEN
+        if slab.dim() != 3 or slab.dtype != torch.float32 or slab.shape[2] != D or not 0 < Rv < slab.shape[1]:
+            raise MspiError("ContrastHead: slab must be fp32 [B, Rv+Ra, %d] with 0 < Rv = %s < Rv+Ra, got %s %s"
+                            % (D, Rv, slab.dtype, tuple(slab.shape)))
+        if len(ts) != 36:
+            raise MspiError("ContrastHead: expected 36 tensors after Rv (vis_projector, mlp_vis, aud_projector, mlp_aud), got %d" % len(ts))
+        want = ((Hd, D), (Hd,), (Hd,), (Hd,), (Hd, Hd), (Hd,), (Hd,), (Hd,), (Hd, Hd), (Hd,), (Hd,), (Hd,),
+                (D, Hd), (D,), (D,), (D,), (Hd, D), (Hd,))
+        for side, off in (("vis", 0), ("aud", 18)):
+            for name, t, shape in zip(CONTRAST_TENSORS, ts[off:off + 18], want):
+                if tuple(t.shape) != shape or t.device != slab.device:
+                    raise MspiError("ContrastHead: %s %s is %s on %s, the head has %s on %s"
+                                    % (side, name, tuple(t.shape), t.device, shape, slab.device))
+        slab = slab.detach().contiguous()
+        B, R, _ = slab.shape
+        with torch.no_grad():
+            x = E.CL(slab.view(-1), 0, B, R, 1, 1, D, D)
+            loss, pooled, vis, aud = contrast_forward(x.tokens(0, Rv, 1, 1), x.tokens(Rv, R - Rv, 1, 1),
+                                                      pack_contrast_side(ts[:18]), pack_contrast_side(ts[18:]))
+        kept = [pooled]
+        for emb, pred, zs, ys in (vis, aud):
+            kept += [pred.buf] + [z.buf for z in zs] + [y.buf for y in ys]
+        ctx.save_for_backward(*kept, *ts)
+        ctx.geom = (B, R, Rv)
+        return loss[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        saved = ctx.saved_tensors
+        B, R, Rv = ctx.geom
+        D = CONTRAST_DIM
+        need = ctx.needs_input_grad
+        pooled, kept, ts = saved[0], saved[1:19], saved[19:]
+        g = G.detach().float().reshape(1).contiguous()
+        grads = [None] * 38
+        dslab = None
+        if need[0]:
+            dslab = E.alloc(B, R, 1, 1, D, pooled.device)
+        for side, (r0, rows) in enumerate(((0, Rv), (Rv, R - Rv))):
+            first = 2 + 18 * side                                       # this modality's tensors in the argument list
+            w = ts[18 * side:18 * side + 18]
+            asked = [need[first + 4 * i] or need[first + 4 * i + 1] for i in range(5)]       # the five Linears
+            asked_ln = [need[first + 4 * i + 2] or need[first + 4 * i + 3] for i in range(4)]
+            lo_lin = min([i for i in range(5) if asked[i]] + [9])       # the lowest Linear and LayerNorm asked for
+            lo_ln = min([i for i in range(4) if asked_ln[i]] + [9])
+            if not need[0] and lo_lin == lo_ln == 9:
+                continue
+            mine, other = kept[9 * side:9 * side + 9], kept[9 * (1 - side):9 * (1 - side) + 9]
+
+            def rows_of(buf):
+                return E.from_rows(buf.view(B, -1))
+            pred, zs, ys = rows_of(mine[0]), [rows_of(t) for t in mine[1:5]], [rows_of(t) for t in mine[5:9]]
+            xs = [rows_of(pooled[side])] + ys                           # the five Linears' inputs
+            d = E.neg_cosine_bwd(pred, rows_of(other[7]), g, 0.5)       # other[7]: the other modality's embedding, detached
+            for i in range(4, -1, -1):
+                if asked[i]:
+                    dW, db = E.linear_wgrad(xs[i], d)
+                    grads[first + 4 * i], grads[first + 4 * i + 1] = dW, db
+                if not (need[0] or lo_lin < i or lo_ln < i):            # nothing below this Linear is asked for
+                    break
+                d = E.conv(d, _pack_t(w[4 * i]))                        # the gradient of the Linear's input
+                if i == 0:
+                    E.mean_rows_bwd(d.as_rows(), dslab.tokens(r0, rows, 1, 1))
+                    break
+                d, dgam, dbet = E.layernorm_act_bwd(d, zs[i - 1], w[4 * i - 2].detach().float().contiguous(), LN_EPS,
+                                                    y=ys[i - 1] if _CONTRAST_ACTS[i - 1] == E.ACT_RELU else None, inplace=True)
+                grads[first + 4 * i - 2], grads[first + 4 * i - 1] = dgam, dbet
+        if need[0]:
+            grads[0] = dslab.as_rows().view(B, R, D)
+        return tuple(gr if need[i] else None for i, gr in enumerate(grads))
+
+
 def compose_lateral(w0, b0, w1):
     """(s,1,1)/s conv after a 1x1x1 conv, no nonlinearity between: one conv with
     W[co,ci,tap] = sum_m W1[co,m,tap] W0[m,ci],  b[co] = sum_{tap,m} W1[co,m,tap] b0[m], composed in fp64."""
@@ -777,6 +914,26 @@ def _cl_view(name, t):
     return E.CL(t, 0, B, T, h, w, c, sW, sN)
 
 
+def _entry_dgrad(G, wc, c0, c, T):
+    """The data gradient of the composed entry conv wc [Co, Cin, s, 1, 1] (kernel == stride along T) for its input channels
+    [c0, c0 + c) from the output gradient G, a dense CL [B,T',h,w,Co]: dense fp32 [B,T,h,w,c], the frames beyond s T' zero."""
+    Co, _, s = wc.shape[:3]
+    if c % 4:
+        raise MspiError("LateralEntry: the data gradient of an input of %d channels is not built (C %% 4 != 0)" % c)
+    B, Tp, h, w = G.N, G.T, G.H, G.W
+    hw = h * w
+    rows = E.conv(G, E.pack_conv(wc[:, c0:c0 + c, :, 0, 0].permute(2, 1, 0).reshape(s * c, Co).contiguous(), None, prec=E.PREC_F32))
+    if s == 1:                                                # rows (b, t, p) x ci: the gradient as it stands
+        dx = rows.as_rows().view(B, Tp, h, w, c)
+    else:                                                     # rows (b, t', p) x (tap, ci): the tap slabs to their frames
+        dx = E.permute(rows, (B, Tp, s, hw, c), (Tp * hw * s * c, hw * s * c, c, s * c, 1)).view(B, Tp * s, h, w, c)
+    if T == Tp * s:
+        return dx
+    out = torch.zeros(B, T, h, w, c, dtype=torch.float32, device=dx.device)
+    out[:, :Tp * s] = dx
+    return out
+
+
 class LateralEntry(torch.autograd.Function):
     """y = LateralEntry.apply(x, x2, w0, b0, w1): the entry conv(s) of a lateral on x, channels-last fp32 [B,T,h,w,C] on the GPU
     (a channel slice of a wider buffer or a token view into a slab is read where it lies), and, x2 not None, on the concat
@@ -787,8 +944,13 @@ class LateralEntry(torch.autograd.Function):
         dW1[co,m,t] = sum_ci dWc[co,ci,t] W0[m,ci] + dbc[co] b0[m]
         dW0[m,ci]   = sum_{co,t} W1[co,m,t] dWc[co,ci,t],   db0[m] = sum_{co,t} W1[co,m,t] dbc[co]
     as two GEMMs on the fp32 MFMA path (E.conv at PREC_F32), the bias terms riding as one more column / row; without w1,
-    dW0 = dWc and db0 = dbc.  Gradients: w0, b0, w1.  x and x2 get NONE: the encoders and the SyncBlock stay frozen, and no
-    kernel here computes the entry convs' data gradient.  No double backward."""
+    dW0 = dWc and db0 = dbc.  Gradients: w0, b0, w1, and x and x2 each only when it requires grad (x2 under
+    trainable(..., sync=True), where it is the visual tokens of the SyncBlock's slab): kernel == stride along T, so
+        dX[b, s t' + tap, p, ci] = sum_co G[b, t', p, co] Wc[co, ci, tap]
+    is one GEMM of the rows (b, t', p) at PREC_F32 with the s C columns (tap, ci), whose s tap slabs E.permute then moves to
+    their frames (as ReadoutTail does for d y4); frames beyond s floor(T / s) are zero.  A dense [B,T,h,w,C] tensor is returned
+    and torch's view backward places x2's into the slab.  With both inputs detached nothing more is launched and dW0, db0, dW1
+    keep their bits.  No double backward."""
 
     @staticmethod
     def forward(ctx, x, x2, w0, b0, w1):
@@ -831,15 +993,24 @@ class LateralEntry(torch.autograd.Function):
         w0, b0 = saved[0], saved[1]
         w1 = saved[2] if has1 else None
         need = ctx.needs_input_grad
-        if not any(need[2:]):
+        if not any(need):
             return None, None, None, None, None
         Gc = _cl5(G.float().contiguous())
+        dxs = [None, None]
+        if need[0] or (has2 and need[1]):
+            wc = compose_lateral(w0, b0, w1)[0] if has1 else w0.detach().float()
+            if need[0]:
+                dxs[0] = _entry_dgrad(Gc, wc, 0, xc.C, xc.T)
+            if has2 and need[1]:
+                dxs[1] = _entry_dgrad(Gc, wc, xc.C, xc2.C, xc2.T)
+        if not any(need[2:]):
+            return dxs[0], dxs[1], None, None, None
         # raw [Co][s][Ci] blocks of the composed conv's gradient, the two inputs' column blocks side by side; dbc once
         dWc, dbc = E.conv_wgrad_entry(xc, Gc, ctx.geoms[0])
         if has2:
             dWc = torch.cat([dWc, E.conv_wgrad_entry(xc2, Gc, ctx.geoms[1])[0]], dim=1)
         if not has1:
-            return None, None, (dWc.contiguous() if need[2] else None), (dbc if need[3] else None), None
+            return dxs[0], dxs[1], (dWc.contiguous() if need[2] else None), (dbc if need[3] else None), None
         Co, Ci, s = dWc.shape[:3]
         mid = w0.shape[0]
         dev = dWc.device
@@ -863,7 +1034,7 @@ class LateralEntry(torch.autograd.Function):
             wt = w1.detach().float()[:, :, :, 0, 0].permute(1, 0, 2).reshape(mid, Co * s).contiguous()
             out = E.conv(E.from_rows(a), E.pack_conv(wt, None, prec=E.PREC_F32)).as_rows(mid)      # [Ci + 1, mid]
             dw0, db0 = out[:Ci].t()[:, :, None, None, None], out[Ci]
-        grads = (None, None, dw0, db0, dw1)
+        grads = (dxs[0], dxs[1], dw0, db0, dw1)
         return tuple(gr if need[i] else None for i, gr in enumerate(grads))
 
 

@@ -28,7 +28,7 @@ __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedC
            "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "rowgate_bwd", "upsample_sum_bwd", "gelu_bwd",
            "layernorm_bwd", "dwconv_wgrad", "conv_wgrad_entry", "conv_wgrad_entry_variant", "conv_wgrad_t16",
            "conv_wgrad_t16_variant", "attention_bwd", "layernorm_bwd_wide", "linear_wgrad",
-           "linear_wgrad_variant", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "linear_wgrad_variant", "neg_cosine_bwd", "layernorm_act_bwd", "mean_rows_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 # ----------------------------------------------------------------------------- conv autotuning
@@ -1540,6 +1540,68 @@ def linear_wgrad(x, dy, bias=True):
         check(lib.mspi_linear_wgrad(x.ptr, x.ld, dy.ptr, dy.ld, dW.data_ptr(), db.data_ptr() if bias else None, ws.data_ptr(),
                                     M, N, K, _stream()), "mspi_linear_wgrad")
     return dW, db
+
+
+# ----------------------------------------------------------------------------- contrastive head (csrc/contrast_bwd.hip)
+LN_ACT_BWD_MAX_CH = 2048                 # widest row mspi_layernorm_act_bwd takes
+LN_ACT_BWD_ROWS = 8                      # rows per workgroup record of mspi_layernorm_act_bwd
+
+
+def neg_cosine_bwd(p, z, g, scale):
+    """The gradient of neg_cosine(p, z, out, scale, .) with respect to p for the gradient g of out, a one-element fp32 tensor on
+    the device (read by the kernel: nothing synchronises); z is a constant.  p, z: dense CLs of N rows x C columns.  Returns dp,
+    a CL like p."""
+    lib = _lib.load()
+    _need_gpu(p.buf)
+    if (z.M, z.C) != (p.M, p.C) or p.ld != p.C or z.ld != z.C or not p.dense or not z.dense or z.buf.device != p.buf.device:
+        raise MspiError("neg_cosine_bwd: p and z must be dense rows of one shape on one device (p %d x %d, z %d x %d)"
+                        % (p.M, p.C, z.M, z.C))
+    if g.dtype != torch.float32 or g.numel() != 1 or g.device != p.buf.device:
+        raise MspiError("neg_cosine_bwd: g must be one fp32 element on %s, got %s %s on %s"
+                        % (p.buf.device, g.dtype, tuple(g.shape), g.device))
+    dp = alloc(p.N, p.T, p.H, p.W, p.C, p.buf.device, ld=p.C)
+    with _Timed("neg_cosine_bwd", 8.0 * p.M * p.C, 12.0 * p.M * p.C, "N=%d C=%d" % (p.M, p.C)):
+        check(lib.mspi_neg_cosine_bwd(p.ptr, z.ptr, g.data_ptr(), dp.ptr, p.M, p.C, float(scale), _stream()), "mspi_neg_cosine_bwd")
+    return dp
+
+
+def layernorm_act_bwd(dy, x, gamma, eps=1e-5, y=None, inplace=False):
+    """Backward of act(layernorm(x, gamma, beta, eps)) for rows of up to 2048 channels (mspi_layernorm_act_bwd): act is the ReLU
+    where the forward's output y is given (dy counts only where y > 0), the identity with y None.  inplace=True writes dx over
+    dy.  Returns (dx, dgamma, dbeta): a CL like x and two fp32 [C]."""
+    lib = _lib.load()
+    _need_gpu(x.buf)
+    M, Cc = _bn_rows("layernorm_act_bwd", x)
+    if Cc > LN_ACT_BWD_MAX_CH:
+        raise MspiError("layernorm_act_bwd: rows of %d channels, at most %d" % (Cc, LN_ACT_BWD_MAX_CH))
+    _rows_like("layernorm_act_bwd", "dy", dy, x)
+    if y is not None:
+        _rows_like("layernorm_act_bwd", "y", y, x)
+    dev = x.buf.device
+    gp = _bn_vec("layernorm_act_bwd", "gamma", gamma, Cc, dev)
+    dx = dy if inplace else alloc(x.N, x.T, x.H, x.W, x.C, dev)
+    dgb = torch.empty(2, Cc, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_layernorm_act_bwd_ws_bytes(M, Cc) // 4, dtype=torch.float32, device=dev)       # stream-ordered
+    with _Timed("layernorm_act_bwd", 20.0 * M * Cc, 4.0 * M * Cc * (3 if y is None else 4), "M=%d C=%d" % (M, Cc)):
+        check(lib.mspi_layernorm_act_bwd(x.ptr, x.ld, dy.ptr, dy.ld, None if y is None else y.ptr, 0 if y is None else y.ld, gp,
+                                         float(eps), dx.ptr, dx.ld, dgb[0].data_ptr(), dgb[1].data_ptr(), ws.data_ptr(), M, Cc,
+                                         _stream()), "mspi_layernorm_act_bwd")
+    return dx, dgb[0], dgb[1]
+
+
+def mean_rows_bwd(g, dx, accumulate=False):
+    """The adjoint of mean_rows(x, N, R, out): dx[n, r, :] (+)= g[n, :] / R over the R = T*H*W rows of each sample of the CL dx
+    (a token view into a slab: rows outside it are not touched).  g: contiguous fp32 [N, C]."""
+    lib = _lib.load()
+    _need_gpu(dx.buf)
+    if g.dtype != torch.float32 or tuple(g.shape) != (dx.N, dx.C) or not g.is_contiguous() or g.device != dx.buf.device:
+        raise MspiError("mean_rows_bwd: g must be contiguous fp32 [%d, %d] on %s, got %s %s on %s"
+                        % (dx.N, dx.C, dx.buf.device, g.dtype, tuple(g.shape), g.device))
+    R = dx.T * dx.H * dx.W
+    with _Timed("mean_rows_bwd", 1.0 * dx.M * dx.C, 4.0 * dx.M * dx.C * (2 if accumulate else 1), "N=%d R=%d C=%d" % (dx.N, R, dx.C)):
+        check(lib.mspi_mean_rows_bwd(g.data_ptr(), dx.ptr, dx.ld, dx.sN, dx.N, R, dx.C, 1 if accumulate else 0, _stream()),
+              "mspi_mean_rows_bwd")
+    return dx
 
 
 def mean_rows(x, N, R, out):

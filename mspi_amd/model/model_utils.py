@@ -21,9 +21,9 @@ import torch.nn as nn
 from .. import engine as E
 from .._lib import MspiError
 from ..autograd import Adapter as AdapterTrain
-from ..autograd import (STAGE_NAMES, STAGES, Fusion, LateralBlock, LateralEntry, ReadoutHead, ReadoutTail, compose_lateral,
-                        convnext_block_forward, pack_convnext_block, pack_lateral_entry, pack_readout_tail, r0_parts, reaches,
-                        readout_tail_forward, stage_rank, stages_upto)
+from ..autograd import (STAGE_NAMES, STAGES, SYNC_PREFIXES, ContrastHead, Fusion, LateralBlock, LateralEntry, ReadoutHead,
+                        ReadoutTail, compose_lateral, convnext_block_forward, pack_convnext_block, pack_lateral_entry,
+                        pack_readout_tail, r0_parts, reaches, readout_tail_forward, stage_rank, stages_upto, sync_block)
 from ..backbones.convnext import ConvNeXtTinyFeatures
 from ..backbones.resnet import get_resnet18
 from ..module import HipModule, to_cl
@@ -639,7 +639,7 @@ class _SaliencyBase(HipModule):
 
     TAIL_PARAMS = STAGES[0].params
 
-    def trainable(self, what):
+    def trainable(self, what, sync=False):
         """trainable("adapter"): on top of what "lateral_entries" trains, the adapter's Inception -- the eight conv -> BatchNorm3d
         -> ReLU layers of adapter.conv, 24 more tensors: 107 in all with the all-composed encoders, 105 with s3d, 103 with
         slowfast.  A forward with grad enabled stops the image branch IN FRONT of the Inception and hands its 416-wide input to
@@ -669,12 +669,31 @@ class _SaliencyBase(HipModule):
         trainable("readout_tail"): the three convs readout[8], readout[10], readout[12] become trainable on top of a frozen
         network -- every other parameter gets requires_grad_(False), and a forward with grad enabled computes the features in
         front of readout[8] as in inference (eval BatchNorm, folded) and hands them to autograd.ReadoutTail.
-        trainable(None) switches back and restores the flags found at switch-on.  Off by default."""
+        trainable(None) switches back and restores the flags found at switch-on.  Off by default.
+        sync=True, a switch BESIDE the ladder (the six stages stay six): on top of the stage's tensors the SyncBlock and the
+        contrastive head train -- the 39 tensors of aud_vis_sync_block, the 12 each of vis_projector and aud_projector and the 6
+        each of mlp_vis and mlp_aud, 75 more: 182 in all on "adapter" with the all-composed encoders (180 with s3d, 178 with
+        slowfast), 158 on "lateral_entries".  Accepted only on AudioVisualSaliencyModel and only where `what` reaches
+        "lateral_entries": the SyncBlock's only path to the map is latlayer_3's entry conv; anything else is refused by name.
+        A forward with grad enabled then launches neither SyncBlock.run nor the contrastive side branch: v4 and the audio map
+        go, as fp32 rows, to autograd.sync_block, whose slab hands its visual tokens to autograd.LateralEntry as x2 (which
+        returns their gradient) and the whole of itself to autograd.ContrastHead, and forward returns (map, loss_av), BOTH
+        carrying a graph -- engine_train.train_one_epoch's gamma * aux then trains the 36 tensors of the head, which nothing
+        else reaches.  v4 and the audio map get no gradient: the three encoders stay frozen.  All added modules are LayerNorm
+        and Linear, so none gains a mode.  Under torch.no_grad(), or without the keyword, nothing changes."""
         d = self.__dict__
+        if sync:
+            if not hasattr(self, "aud_vis_sync_block"):
+                raise MspiError("trainable(%r, sync=True): %s has neither a SyncBlock nor a contrastive head; sync=True is for "
+                                "AudioVisualSaliencyModel" % (what, type(self).__name__))
+            if what is None or (what in STAGE_NAMES and not reaches(what, "lateral_entries")):
+                raise MspiError("trainable(%r, sync=True): the SyncBlock reaches the map only through latlayer_3's entry conv, so "
+                                "sync=True needs a stage that trains it: %s" % (what, " or ".join(repr(n) for n in STAGE_NAMES[4:])))
         if what is None:
             for p, flag in d.pop("_trainable_saved", []):
                 p.requires_grad_(flag)
             d["_trainable"] = None
+            d["_trainable_sync"] = False
             return self
         if what not in STAGE_NAMES:
             raise MspiError("trainable: %r is not a trainable part of this model (only %s and %r are)"
@@ -684,8 +703,9 @@ class _SaliencyBase(HipModule):
         if d.get("_trainable") is None:
             d["_trainable_saved"] = [(p, p.requires_grad) for p in self.parameters()]
         d["_trainable"] = what
+        d["_trainable_sync"] = bool(sync)
         prefixes = tuple(p.format(k=k, last=len(getattr(self, "latlayer_%d" % k)) - 1)
-                         for st in stages_upto(what) for p in st.params for k in range(4))
+                         for st in stages_upto(what) for p in st.params for k in range(4)) + (SYNC_PREFIXES if sync else ())
         for name, p in self.named_parameters():
             p.requires_grad_(name.startswith(prefixes))
         return self
@@ -731,9 +751,11 @@ class _SaliencyBase(HipModule):
 
     def _tail_with_grad(self, y):
         """The rest of a forward that carries a graph, from what _forward stopped at (_training_tail) to the map: the stages'
-        autograd Functions on the live tensors, lowest part of the network first."""
+        autograd Functions on the live tensors, lowest part of the network first.  Returns (map, loss_av): loss_av carries the
+        graph of autograd.ContrastHead under trainable(..., sync=True) and is None otherwise."""
         what = self.__dict__.get("_trainable")
         r = self.readout
+        loss_av = None
         if reaches(what, "fusion"):
             idle = [n for n, m in self._batch_stat_modules().items() if not m.training]
             if idle:
@@ -743,7 +765,16 @@ class _SaliencyBase(HipModule):
             lats, m = list(y[:4]), y[4].as_nthwc()
             seqs = [getattr(self, "latlayer_%d" % k) for k in range(4)]
             if reaches(what, "lateral_entries"):      # the encoder maps: the entry convs run here and their outputs carry a graph
-                lats = [LateralEntry.apply(xs[0].as_nthwc(), xs[1].as_nthwc() if len(xs) == 2 else None, seq[0].weight, seq[0].bias,
+                lats = [[x.as_nthwc() for x in xs] for xs in lats]
+                if self.__dict__.get("_trainable_sync"):
+                    # lats[3] is (v4, the audio map): the SyncBlock runs here, its slab carries a graph over the 39 tensors,
+                    # its visual tokens are latlayer_3's second input and the whole of it the contrastive head's
+                    v4, aud = lats[3]
+                    slab = sync_block(self.aud_vis_sync_block, v4, aud)
+                    Rv = v4.shape[1] * v4.shape[2] * v4.shape[3]
+                    lats[3] = [v4, slab[:, :Rv].view(v4.shape[:4] + (slab.shape[2],))]
+                    loss_av = ContrastHead.apply(slab, Rv, *self._contrast_tensors())
+                lats = [LateralEntry.apply(xs[0], xs[1] if len(xs) == 2 else None, seq[0].weight, seq[0].bias,
                                            seq[1].weight if len(seq) == 3 else None) for xs, seq in zip(lats, seqs)]
             else:
                 lats = [s.as_nthwc() for s in lats]
@@ -764,7 +795,7 @@ class _SaliencyBase(HipModule):
             y = ReadoutHead.apply(*[s if torch.is_tensor(s) else s.as_nthwc() for s in y], *ts, *bns)
         else:
             y = y.as_nthwc()
-        return ReadoutTail.apply(y, *[self.get_parameter(n) for n in self.TAIL_PARAMS])
+        return ReadoutTail.apply(y, *[self.get_parameter(n) for n in self.TAIL_PARAMS]), loss_av
 
     def _head_tensors(self):
         """The ten tensors of readout[0], [1], [2], [4], [5] in the order of autograd.ReadoutHead's arguments and the two BatchNorm
@@ -856,15 +887,23 @@ class AudioVisualSaliencyModel(_SaliencyBase):
         y = E.layernorm(E.conv(emb, p[3][0]), p[3][1], p[3][2], 1e-5, act=E.ACT_RELU)
         return emb, E.conv(y, p[4])
 
+    def _contrast_tensors(self):
+        """The 36 tensors of vis_projector, mlp_vis, aud_projector and mlp_aud, each in module order: autograd.ContrastHead's
+        arguments."""
+        return [t for m in (self.vis_projector, self.mlp_vis, self.aud_projector, self.mlp_aud) for t in m.parameters()]
+
     def forward(self, clips, audios, frame_feats=None):
         """frame_feats: optional (f1 [B*T,h,w,96], f0 [B*T,h/2,w/2,320]) from encode_frames() for the clips' frames in
         (b t) order -- the image branch then starts at the adapter (sliding-window inference re-uses 15 of 16 frames).
         After trainable("readout_tail") or trainable("readout") and with grad enabled, the map carries the graph of
-        autograd.ReadoutTail (and autograd.ReadoutHead)."""
+        autograd.ReadoutTail (and autograd.ReadoutHead); after trainable(..., sync=True) loss_av carries one too."""
         tail = self._training_tail()
         with torch.no_grad():
             y, loss = self._forward(clips, audios, frame_feats, features=tail)
-        return (self._tail_with_grad(y) if tail else y), loss
+        if not tail:
+            return y, loss
+        out, loss_av = self._tail_with_grad(y)
+        return out, (loss if loss_av is None else loss_av)
 
     def _forward(self, clips, audios, frame_feats, features):
         self._check_eval()
@@ -885,7 +924,12 @@ class AudioVisualSaliencyModel(_SaliencyBase):
             v1, v2, v3, v4 = self.visnet.forward_cl(self._pack_clips(clips))
             cat, s0, s1, s2 = self._laterals_012(pk, v1, v2, v3, features)
             fk.join(1)
-            s3, loss = self._sync_and_lateral3(pk, v4, aud, fk, features)
+            if features and self.__dict__.get("_trainable_sync"):
+                # trainable(..., sync=True) in a forward that carries a graph: neither the SyncBlock nor the contrastive branch
+                # is launched; v4 and the audio map travel as fp32 rows to _tail_with_grad (autograd.sync_block, ContrastHead)
+                s3, loss = [E.join_planes(x) if isinstance(x, E.SP) else x for x in (v4, aud)], None
+            else:
+                s3, loss = self._sync_and_lateral3(pk, v4, aud, fk, features)
         return self._fuse_readout(pk, cat, s0, s1, s2, s3, masks, pm, features), loss
 
     def _sync_and_lateral3(self, pk, v4, aud, fk, features=False):
@@ -937,7 +981,7 @@ class VisualSaliencyModel(_SaliencyBase):
         tail = self._training_tail()
         with torch.no_grad():
             y = self._forward(clips, frame_feats, features=tail)
-        return (self._tail_with_grad(y) if tail else y), 0
+        return (self._tail_with_grad(y)[0] if tail else y), 0
 
     def _forward(self, clips, frame_feats, features):
         self._check_eval()

@@ -2,7 +2,7 @@
 
     python -m mspi_amd.train --trainable readout|readout_tail|fusion|lateral_blocks|lateral_entries|adapter --weights w.pt --dataset AVAD --split 1 --model x3dl
         [--path_data ./AuViDataset] [--log_dir ./training_logs] [--save_ckpt_freq 10] [--gamma 1] [--start_epoch 0]
-        [--resolution H W] [--batch 2] [--no_sound] [--workers 8]
+        [--resolution H W] [--batch 2] [--no_sound] [--workers 8] [--sync]
 
 --trainable readout_tail: only readout[8], readout[10] and readout[12] train (model.trainable("readout_tail")); everything in
 front of them is frozen and runs as in inference, with eval BatchNorm folded into the convolutions.
@@ -20,7 +20,14 @@ statistics -- 107 tensors with x3dl, 105 with s3d, 103 with slowfast (autograd.A
 of the masks); with it the visual-only model trains everything upstream trains except the motion encoder.
 Still frozen in all six: the SyncBlock, the contrastive projectors and every encoder (below --trainable adapter also the
 adapter, below --trainable lateral_entries also the laterals' entry convs, with --trainable fusion also the laterals' blocks,
-with --trainable readout and readout_tail also the SA gating).  That is fine-tuning of a released checkpoint's decoder head, not upstream's full training.  As upstream: the training split of
+with --trainable readout and readout_tail also the SA gating).
+--sync, a flag beside the ladder (model.trainable(stage, sync=True)), takes the first two off that list: with --trainable
+lateral_entries or adapter on the audio-visual model the SyncBlock (39 tensors) and the contrastive projectors and predictors
+(36) train too -- 182 tensors with x3dl on adapter, 180 with s3d, 178 with slowfast -- the SyncBlock through latlayer_3's entry
+conv (autograd.sync_block, the data gradient of autograd.LateralEntry) and loss_av, the projectors through loss_av alone
+(autograd.ContrastHead), which train_one_epoch adds to the criterion times --gamma.  With it the audio-visual model trains
+everything upstream trains except the three encoders.  It is refused with --no_sound and below --trainable lateral_entries.
+That is fine-tuning of a released checkpoint's decoder head, not upstream's full training.  As upstream: the training split of
 avsp_dataloader.AudioVisualDataset, AdamW over the parameters that require grad with weight decay 0, cfg.SOLVER.LR for 60
 epochs then a tenth of it every 60 (lr_by_epoch), a state_dict checkpoint every --save_ckpt_freq epochs and at the end
 (inference.build_model loads them), one JSON line per epoch, printed and appended to <log_dir>/log.txt.  One process, one GPU."""
@@ -68,6 +75,16 @@ def check_trainable(value):
     return value
 
 
+def check_sync(trainable, sync, use_sound):
+    """--sync beside --trainable: only on the audio-visual model and only from lateral_entries on."""
+    if sync and not use_sound:
+        raise MspiError("--sync with --no_sound: the visual-only model has neither a SyncBlock nor a contrastive head to train")
+    if sync and trainable not in STAGE_NAMES[4:]:
+        raise MspiError("--sync with --trainable %s: the SyncBlock reaches the map only through latlayer_3's entry conv, so --sync "
+                        "needs --trainable %s" % (trainable, " or ".join(STAGE_NAMES[4:])))
+    return bool(sync)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="python -m mspi_amd.train", description=__doc__.split("\n")[0])
     parser.add_argument("--trainable", default="readout_tail", type=str, help="the part of the model that trains: %s or %s" % (", ".join(STAGE_NAMES[:-1]), STAGE_NAMES[-1]))
@@ -84,6 +101,8 @@ def build_parser():
     parser.add_argument("--clip_size", default=16, type=int)
     parser.add_argument("--batch", default=None, type=int, help="clips per step (default cfg.TRAIN.BATCH_SIZE)")
     parser.add_argument("--no_sound", dest="use_sound", action="store_false", help="the visual-only model")
+    parser.add_argument("--sync", action="store_true", help="also train the SyncBlock and the contrastive head (model.trainable(stage, "
+                        "sync=True)): audio-visual model, --trainable lateral_entries or adapter")
     parser.add_argument("--workers", default=8, type=int, help="host threads decoding JPEGs")
     parser.add_argument("--seed", default=2023, type=int)
     return parser
@@ -121,6 +140,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     print(args)
     check_trainable(args.trainable)
+    check_sync(args.trainable, args.sync, args.use_sound)
     _single_rank()
     if not torch.cuda.is_available():
         raise SystemExit("mspi_amd.train needs an MI355X (no CPU fallback)")
@@ -135,7 +155,7 @@ def main(argv=None):
     I._RESOLUTION[:] = args.resolution
     model = I.build_model(args.model, args.resolution, weight=args.weights or None, use_sound=args.use_sound)
     E.autotune(False)      # the tail is re-packed at every step: nothing to tune once
-    model.trainable(args.trainable)
+    model.trainable(args.trainable, sync=args.sync)
     cfg = model.cfg
     cfg.DATA.USE_SOUND = bool(args.use_sound)
     batch = cfg.TRAIN.BATCH_SIZE if args.batch is None else args.batch

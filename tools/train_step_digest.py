@@ -4,7 +4,9 @@
 
 For each of the four models of tests/test_entry_train.py::MODELS and each of the six stages model.trainable() takes, on a fresh
 model built as tests/test_readout_tail._build builds it: trainable(stage), train(), frozen_encoder(), one forward with grad,
-metrics.SalLoss against a seeded Gaussian density, backward.  Autotuning is off and the autotune cache empty, so the library's
+metrics.SalLoss against a seeded Gaussian density, backward.  On the audio-visual models a seventh case, "adapter+sync":
+trainable("adapter", sync=True), and loss_av added to the criterion before the backward (its own line, `out loss_av`).  On a
+commit whose trainable() has no such keyword that case is left out.  Autotuning is off and the autotune cache empty, so the library's
 own kernel choices hold.  One line per case, stage and tensor -- `case stage kind name crc32 numel` -- for the output map,
 every gradient and every buffer the step moved (the BatchNorm running statistics).  --launches: also the engine.Profiler
 summary of one more trainable("adapter") step on av_x3dl_64, one `launch kernel calls` line per kernel name.  Only the public
@@ -23,6 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 STAGES = ("readout_tail", "readout", "fusion", "lateral_blocks", "lateral_entries", "adapter")
+SYNC = "adapter+sync"                    # trainable("adapter", sync=True): the audio-visual models only
 
 
 def crc(t):
@@ -43,14 +46,14 @@ def density(B, H, W, seed=900):
     return torch.from_numpy(m)
 
 
-def step(m, args, label, loss):
+def step(m, args, label, loss, sync=False):
     for p in m.parameters():
         p.grad = None
-    out = m(*args)[0]
-    assert out.requires_grad
-    loss(out, label).backward()
+    out, aux = m(*args)
+    assert out.requires_grad and (not sync or aux.requires_grad)
+    (loss(out, label) + aux if sync else loss(out, label)).backward()
     torch.cuda.synchronize()
-    return out
+    return out, aux
 
 
 def main(argv=None):
@@ -71,15 +74,24 @@ def main(argv=None):
         _, _, make, clips, audio = _build(golden, case, name, cls, dev)
         args = (clips, audio) if cls == "AudioVisualSaliencyModel" else (clips,)
         label = density(clips.shape[0], clips.shape[3], clips.shape[4]).to(dev)
-        for stage in STAGES:
+        for stage in STAGES + ((SYNC,) if len(args) == 2 else ()):
             with contextlib.redirect_stdout(sys.stderr):      # the constructors announce their encoder
                 m = make().to(dev)
-            m.trainable(stage)
+            sync = stage == SYNC
+            if sync:
+                try:
+                    m.trainable("adapter", sync=True)
+                except TypeError:                             # an older commit: no keyword, no case
+                    continue
+            else:
+                m.trainable(stage)
             m.train()
             m.frozen_encoder()
             before = {k: v.clone() for k, v in m.named_buffers()}
-            out = step(m, args, label, M.SalLoss())
+            out, aux = step(m, args, label, M.SalLoss(), sync)
             print("%s %s out map %s %d" % (case, stage, crc(out), out.numel()))
+            if sync:
+                print("%s %s out loss_av %s %d" % (case, stage, crc(aux), aux.numel()))
             for n, p in sorted(m.named_parameters()):
                 if p.grad is not None:
                     print("%s %s grad %s %s %d" % (case, stage, n, crc(p.grad), p.grad.numel()))
