@@ -347,6 +347,24 @@ _CONTRAST_SIGNATURES = {
 
 CONTRAST_EXPORTS = tuple(_CONTRAST_SIGNATURES)
 
+# The X3D block's backward declared in include/mspi_x3d_train_hip.h (csrc/x3d_bwd.hip): a ninth table, likewise
+_X3D_SIGNATURES = {
+    "mspi_dwconv3_wgrad_supported": (C.c_int, [C.POINTER(DwConvDesc)]),
+    "mspi_dwconv3_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(DwConvDesc)]),
+    "mspi_dwconv3_wgrad": (C.c_int, [C.POINTER(DwConvDesc), _P, _P, _P, _P, _P, _P]),
+    "mspi_bn_gate_act_fwd": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                       C.c_int32, _P]),
+    "mspi_gate_swish_bwd_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "mspi_gate_swish_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32,
+                                      C.c_int32, _P]),
+    "mspi_se_train_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mspi_se_train_bwd_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "mspi_se_train_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mspi_relu_mask_add": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P]),
+}
+
+X3D_EXPORTS = tuple(_X3D_SIGNATURES)
+
 _lib = None
 
 
@@ -367,7 +385,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
             list(_ENTRY_SIGNATURES.items()) + list(_ADAPTER_SIGNATURES.items()) + list(_SYNC_SIGNATURES.items()) + list(_LINEAR_SIGNATURES.items()) + \
-            list(_CONTRAST_SIGNATURES.items()):
+            list(_CONTRAST_SIGNATURES.items()) + list(_X3D_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

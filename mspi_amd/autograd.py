@@ -23,7 +23,11 @@ TransformerBlock: one pre-LN transformer Block of the SyncBlock (model/model_uti
 eleven tensors.  SyncEmbed: the embedding in front of the blocks (vis_proj, vis_norm, aud_norm, the sinusoid tables as
 constants); sync_block: the two chained, the whole SyncBlock over its 39 tensors.  ContrastHead: the contrastive head behind it
 (the two pooled rows, projectors, predictors and the two negative cosines) over the slab and its 36 tensors.  No stage of the
-ladder holds them: trainable(what, sync=True) switches them on beside a stage that reaches "lateral_entries"."""
+ladder holds them: trainable(what, sync=True) switches them on beside a stage that reaches "lateral_entries".
+
+X3DBlock: one stride-1 X3D residual block without branch1 (backbones/blocks3d.py: ResBlock over an X3DTransform) with its three
+BatchNorm layers on BATCH statistics, over its input and 13 tensors; x3d_blocks chains it over the blocks of a ResStage.  No
+model reaches them yet: the stage heads and the stem have no backward."""
 import collections
 
 import torch
@@ -1166,3 +1170,176 @@ class Adapter(torch.autograd.Function):
                     dy = E.conv(dz, _pack_dgrad(wl, pad))
             c0 += cw
         return tuple(g if g is None or need[i] else None for i, g in enumerate(grads))
+
+
+# ------------------------------------------------------------------------------------------------ X3D residual block
+X3D_BLOCK_TENSORS = ("a.weight", "a_bn.weight", "a_bn.bias", "b.weight", "b_bn.weight", "b_bn.bias", "se.fc1.weight", "se.fc1.bias",
+                     "se.fc2.weight", "se.fc2.bias", "c.weight", "c_bn.weight", "c_bn.bias")
+
+
+def _bn_stats_sliced(x, eps):
+    """(mean, biased var, rstd) of the CL x over _bn_slices(x.C)."""
+    stats = [E.bn_stats(x.slice(c0, c), eps) for c0, c in _bn_slices(x.C)]
+    return stats[0] if len(stats) == 1 else tuple(torch.cat(ts) for ts in zip(*stats))
+
+
+def _bn_bwd_sliced(dy, x, mean, rstd, gamma, y=None):
+    """E.bn_bwd over _bn_slices(x.C): (dx, a new CL like x, dgamma, dbeta)."""
+    dev = x.buf.device
+    dx = E.alloc(x.N, x.T, x.H, x.W, x.C, dev)
+    dgam, dbet = (torch.empty(x.C, dtype=torch.float32, device=dev) for _ in range(2))
+    for c0, c in _bn_slices(x.C):
+        _, dg, db = E.bn_bwd(dy.slice(c0, c), x.slice(c0, c), mean[c0:c0 + c].contiguous(), rstd[c0:c0 + c].contiguous(),
+                             gamma[c0:c0 + c].contiguous(), y=None if y is None else y.slice(c0, c), dx=dx.slice(c0, c))
+        dgam[c0:c0 + c], dbet[c0:c0 + c] = dg, db
+    return dx, dgam, dbet
+
+
+def _bn_relu_sliced(x, mean, rstd, gamma, beta):
+    """relu(bn(x)) on given statistics by bn_relu_train's launches: E.bn_apply over _bn_slices(x.C), the forward's bits."""
+    out = E.alloc(x.N, x.T, x.H, x.W, x.C, x.buf.device)
+    for c0, c in _bn_slices(x.C):
+        E.bn_apply(x.slice(c0, c), mean[c0:c0 + c].contiguous(), rstd[c0:c0 + c].contiguous(), gamma[c0:c0 + c].contiguous(),
+                   beta[c0:c0 + c].contiguous(), act=E.ACT_RELU, out=out.slice(c0, c))
+    return out
+
+
+class X3DBlock(torch.autograd.Function):
+    """y = X3DBlock.apply(x, wa, ga, ba, wb, gb, bb, w1, b1, w2, b2, wc, gc, bc, bn_a, bn_b, bn_c): one stride-1 X3D residual
+    block without branch1 (SlowFast/resnet_helper.py:213-360, 490-616 upstream) with its three BatchNorm layers on BATCH
+    statistics (eps 1e-5):
+        z_a = a(x); t = relu(bn_a(z_a)); v0 = b(t); v = bn_b(v0); g = sigmoid(fc2(relu(fc1(mean_THW(v))))); s = swish(v g);
+        z_c = c(s); y = relu(x + bn_c(z_c)).
+    x fp32 channels-last [B,T,h,w,dim_out] on the GPU; the tensors in their nn layouts, X3D_BLOCK_TENSORS order; w1, b1, w2, b2
+    None for a block without `se` (g = 1).  bn_*: (running_mean, running_var, num_batches_tracked), updated in place as
+    nn.BatchNorm3d.train() with momentum 0.1 updates them, or None to skip that.  dim_out a multiple of 32 and dim_inner of 4
+    (what mspi_linear_wgrad takes), at least two rows.  The forward runs the unfolded convs on packs of the live values, bn_stats
+    over _bn_slices, and keeps x, the pre-norm z_a, v0, z_c, the output y, the statistics and the SE's p, h, gate; t and s are
+    computed again in the backward.  Backward: bn_bwd under y's mask, linear_wgrad for `c` and (operands exchanged, then
+    transposed: dim_inner need not be a multiple of 32) for `a`, the data gradients on _pack_t at PREC_F32, gate_swish_bwd,
+    se_train_bwd and mean_rows_bwd, dwconv3_wgrad, the depthwise conv on the flipped taps, relu_mask_add for the skip path.
+    Gradients: x and the 13 tensors, each only when it requires grad.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, wa, ga, ba, wb, gb, bb, w1, b1, w2, b2, wc, gc, bc, bn_a, bn_b, bn_c):
+        if x.dim() != 5 or x.dtype != torch.float32:
+            raise MspiError("X3DBlock: x must be fp32 [B,T,h,w,dim_out] (channels-last), got %s %s" % (x.dtype, tuple(x.shape)))
+        B, T, h, w, D = x.shape
+        Ci = wa.shape[0] if wa.dim() == 5 else -1
+        se = [t is not None for t in (w1, b1, w2, b2)]
+        if any(se) != all(se):
+            raise MspiError("X3DBlock: se.fc1 / se.fc2 must be given whole (four tensors) or not at all (four None)")
+        se = all(se)
+        F = b1.numel() if se else 0
+        want = ((Ci, D, 1, 1, 1), (Ci,), (Ci,), (Ci, 1, 3, 3, 3), (Ci,), (Ci,), (F, Ci, 1, 1, 1), (F,), (Ci, F, 1, 1, 1), (Ci,),
+                (D, Ci, 1, 1, 1), (D,), (D,))
+        for name, t, shape in zip(X3D_BLOCK_TENSORS, (wa, ga, ba, wb, gb, bb, w1, b1, w2, b2, wc, gc, bc), want):
+            if t is not None and (tuple(t.shape) != shape or t.device != x.device):
+                raise MspiError("X3DBlock: %s is %s on %s, a block %d -> %d -> %d wide%s has %s on %s"
+                                % (name, tuple(t.shape), t.device, D, Ci, D, " with an SE of %d" % F if se else "", shape, x.device))
+        if D % 32 or Ci % 4 or Ci <= 0:
+            raise MspiError("X3DBlock: dim_out / dim_inner = %d / %d: dim_out must be a multiple of 32 and dim_inner of 4 "
+                            "(X3D-L stages 4 and 5: 96 / 216, 192 / 432)" % (D, Ci))
+        if se and not 0 < F <= E.SE_TRAIN_MAX_F:
+            raise MspiError("X3DBlock: se.fc1 has %d output channels, at most %d" % (F, E.SE_TRAIN_MAX_F))
+        M = B * T * h * w
+        if M < 2:
+            raise MspiError("X3DBlock: BatchNorm on batch statistics needs more than one row (B T h w = %d), as torch refuses it" % M)
+        _check_input(x)
+
+        def f(t):
+            return t.detach().float().contiguous()
+        x = x.detach().contiguous()
+        dev = x.device
+        with torch.no_grad():
+            xc = _cl5(x)
+            z_a = E.conv(xc, E.pack_conv(wa, None, None, (1, 1, 1), (0, 0, 0), E.ACT_NONE))
+            t, ma, va, ra = bn_relu_train(z_a, ga, ba, BN_EPS)
+            _bn_running(bn_a, ma, va, M, BN_MOMENTUM)
+            v0 = E.dwconv(t, E.pack_dwconv(wb, None, None, (1, 1, 1), (1, 1, 1), E.ACT_NONE))
+            mb, vb, rb = _bn_stats_sliced(v0, BN_EPS)
+            _bn_running(bn_b, mb, vb, M, BN_MOMENTUM)
+            p = hid = gate = None
+            if se:
+                pool0 = E.mean_rows(v0, B, T * h * w, torch.empty(B, Ci, dtype=torch.float32, device=dev))
+                p, hid, gate = E.se_train_fwd(pool0, mb, rb, f(gb), f(bb), f(w1), f(b1), f(w2), f(b2))
+            s = E.bn_gate_act(v0, mb, rb, f(gb), f(bb), gate=gate, act=E.ACT_SWISH)
+            z_c = E.conv(s, E.pack_conv(wc, None, None, (1, 1, 1), (0, 0, 0), E.ACT_NONE))
+            mc, vc, rc = _bn_stats_sliced(z_c, BN_EPS)
+            _bn_running(bn_c, mc, vc, M, BN_MOMENTUM)
+            y = E.bn_gate_act(z_c, mc, rc, f(gc), f(bc), res=xc, act=E.ACT_RELU)
+        ctx.se = se
+        ctx.save_for_backward(x, z_a.buf, v0.buf, z_c.buf, y.buf, ma, ra, mb, rb, mc, rc, wa, ga, ba, wb, gb, bb, wc, gc,
+                              *((p, hid, gate, w1, w2) if se else ()))
+        ctx.geom = tuple((c.off, c.ld) for c in (z_a, v0, z_c, y))
+        return y.as_nthwc()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        saved = ctx.saved_tensors
+        x, zab, v0b, zcb, yb, ma, ra, mb, rb, mc, rc, wa, ga, ba, wb, gb, bb, wc, gc = saved[:19]
+        B, T, h, w, D = x.shape
+        Ci = wa.shape[0]
+        need = ctx.needs_input_grad
+        grads = [None] * 17
+        if not any(need[:14]):
+            return tuple(grads)
+
+        def f(t):
+            return t.detach().float().contiguous()
+
+        def cl(buf, c, geom=None):
+            off, ld = (0, c) if geom is None else geom
+            return E.CL(buf.view(-1), off, B, T, h, w, c, ld)
+        z_a, v0, z_c, y = (cl(b, c, g) for b, c, g in zip((zab, v0b, zcb, yb), (Ci, Ci, D, D), ctx.geom))
+        xc, Gc = cl(x, D), cl(G.float().contiguous(), D)
+        gate = saved[21] if ctx.se else None
+        dz_c, grads[12], grads[13] = _bn_bwd_sliced(Gc, z_c, mc, rc, f(gc), y=y)                 # the block's output is the mask
+        if need[11]:
+            s = E.bn_gate_act(v0, mb, rb, f(gb), f(bb), gate=gate, act=E.ACT_SWISH)
+            grads[11] = E.linear_wgrad(s, dz_c, bias=False)[0].view(D, Ci, 1, 1, 1)
+        if any(need[:11]):
+            ds = E.conv(dz_c, _pack_t(wc))
+            dv, dgate = E.gate_swish_bwd(ds, v0, mb, rb, f(gb), f(bb), gate=gate, inplace=True)
+            if ctx.se:
+                p, hid, _, w1, w2 = saved[19:]
+                grads[7], grads[8], grads[9], grads[10], dp = E.se_train_bwd(dgate, gate, hid, p, f(w1), f(w2))
+                E.mean_rows_bwd(dp, dv, accumulate=True)                                         # completes dv
+        if any(need[:7]):
+            dv0, grads[5], grads[6] = _bn_bwd_sliced(dv, v0, mb, rb, f(gb))
+        if any(need[:5]):
+            t = _bn_relu_sliced(z_a, ma, ra, f(ga), f(ba))
+            if need[4]:
+                grads[4] = E.dwconv3_wgrad(t, dv0)[0]
+        if any(need[:4]):
+            dt = E.dwconv(dv0, E.pack_dwconv(wb.detach().flip(2, 3, 4), None, None, (1, 1, 1), (1, 1, 1), E.ACT_NONE))
+            dz_a, grads[2], grads[3] = _bn_bwd_sliced(dt, z_a, ma, ra, f(ga), y=t)
+            if need[1]:
+                # operands exchanged: [dim_out][dim_inner] = dW_a^T, the same sums; 432 is no multiple of 32, 192 and 96 are
+                grads[1] = E.linear_wgrad(dz_a, xc, bias=False)[0].t().contiguous().view(Ci, D, 1, 1, 1)
+            if need[0]:
+                dx = E.conv(dz_a, _pack_t(wa))
+                grads[0] = E.relu_mask_add(dx, Gc, y).as_nthwc()                                 # the skip path
+        return tuple(g if g is None or need[i] else None for i, g in enumerate(grads))
+
+
+def x3d_blocks(stage, x, start=1, stop=None):
+    """Blocks start .. stop - 1 (None: to the end) of the single pathway of the ResStage `stage`, chained as X3DBlock on
+    ResBlock.tensors(): x fp32 channels-last [B,T,h,w,dim_out] on the GPU.  The stage's first block (stride-2 `b`, branch1) has
+    no backward yet and is refused by name, like any other block with branch1 or a stride.  Returns the last block's output
+    with a graph over every tensor of the blocks (and x where it requires grad)."""
+    if stage.num_pathways != 1:
+        raise MspiError("x3d_blocks: the stage has %d pathways, X3D has one" % stage.num_pathways)
+    blocks = stage.blocks(0)
+    stop = len(blocks) if stop is None else stop
+    if not 0 <= start < stop <= len(blocks):
+        raise MspiError("x3d_blocks: blocks %d .. %d of a stage of %d" % (start, stop - 1, len(blocks)))
+    for i in range(start, stop):
+        blk = blocks[i]
+        tr = blk.branch2
+        if hasattr(blk, "branch1") or tuple(tr.a.stride) != (1, 1, 1) or tuple(tr.b.stride) != (1, 1, 1):
+            raise MspiError("x3d_blocks: pathway0_res%d has %s: only stride-1 blocks without branch1 have a backward (the stage "
+                            "heads are still frozen)" % (i, "branch1" if hasattr(blk, "branch1") else "a stride of %s" % (tuple(tr.b.stride),)))
+        x = X3DBlock.apply(x, *blk.tensors())
+    return x

@@ -279,6 +279,19 @@ class ResBlock(HipModule):
                                cin_stored=E.rup4(c.in_channels))
         return None
 
+    def tensors(self):
+        """The block's tensors and BatchNorm buffer triples in the order of autograd.X3DBlock's arguments after x: the 13 of
+        autograd.X3D_BLOCK_TENSORS (None four times where branch2 has no `se`), then a_bn, b_bn, c_bn's (running_mean,
+        running_var, num_batches_tracked).  branch1 is not among them: X3DBlock has none."""
+        t = self.branch2
+        if not isinstance(t, X3DTransform):
+            raise E.MspiError("ResBlock.tensors: branch2 is a %s, only an X3DTransform has a training path" % type(t).__name__)
+        se = getattr(t, "se", None)
+        fc = (None,) * 4 if se is None else (se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias)
+        bns = tuple((bn.running_mean, bn.running_var, bn.num_batches_tracked) for bn in (t.a_bn, t.b_bn, t.c_bn))
+        return (t.a.weight, t.a_bn.weight, t.a_bn.bias, t.b.weight, t.b_bn.weight, t.b_bn.bias) + fc + \
+            (t.c.weight, t.c_bn.weight, t.c_bn.bias) + bns
+
     def run(self, x, out=None, **seam):
         skip = E.conv(x, self.pk) if self.pk is not None else x
         return self.branch2.run(x, skip, out=out, **seam)

@@ -28,7 +28,8 @@ __all__ = ["CL", "SP", "alloc", "alloc_sp", "pack_conv", "pack_dwconv", "PackedC
            "conv_wgrad_wide_variant", "bn_stats", "bn_apply", "bn_bwd", "rowgate_bwd", "upsample_sum_bwd", "gelu_bwd",
            "layernorm_bwd", "dwconv_wgrad", "conv_wgrad_entry", "conv_wgrad_entry_variant", "conv_wgrad_t16",
            "conv_wgrad_t16_variant", "attention_bwd", "layernorm_bwd_wide", "linear_wgrad",
-           "linear_wgrad_variant", "neg_cosine_bwd", "layernorm_act_bwd", "mean_rows_bwd", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
+           "linear_wgrad_variant", "neg_cosine_bwd", "layernorm_act_bwd", "mean_rows_bwd", "dwconv3_wgrad", "bn_gate_act",
+           "gate_swish_bwd", "se_train_fwd", "se_train_bwd", "relu_mask_add", "ACT_NONE", "ACT_RELU", "ACT_GELU", "ACT_SIGMOID", "ACT_SWISH"]
 
 
 # ----------------------------------------------------------------------------- conv autotuning
@@ -1601,6 +1602,161 @@ def mean_rows_bwd(g, dx, accumulate=False):
     with _Timed("mean_rows_bwd", 1.0 * dx.M * dx.C, 4.0 * dx.M * dx.C * (2 if accumulate else 1), "N=%d R=%d C=%d" % (dx.N, R, dx.C)):
         check(lib.mspi_mean_rows_bwd(g.data_ptr(), dx.ptr, dx.ld, dx.sN, dx.N, R, dx.C, 1 if accumulate else 0, _stream()),
               "mspi_mean_rows_bwd")
+    return dx
+
+
+# ----------------------------------------------------------------------------- X3D block backward (csrc/x3d_bwd.hip)
+X3D_TRAIN_MAX_CH = 4096                  # widest row the mspi_x3d_train_hip.h entry points take
+SE_TRAIN_MAX_F = 64                      # widest fc1.out_channels mspi_se_train_fwd / _bwd take
+DWCONV3_WGRAD_RECORDS = 256              # records the band rule of mspi_dwconv3_wgrad aims at
+GATE_SWISH_BWD_ROWS = 32                 # rows of a sample per record of mspi_gate_swish_bwd
+
+
+def _x3d_rows(name, what, t, ref=None):
+    """A CL of dense samples, a multiple of 4 wide and at most X3D_TRAIN_MAX_CH, on the GPU; shaped like ref where given."""
+    _need_gpu(t.buf)
+    if not t.dense or t.Cs != t.C or t.C > X3D_TRAIN_MAX_CH:
+        raise MspiError("%s: %s must be dense rows with a channel count that is a multiple of 4, at most %d (%d rows x %d)"
+                        % (name, what, X3D_TRAIN_MAX_CH, t.M, t.C))
+    if ref is not None and ((t.N, t.T, t.H, t.W, t.C) != (ref.N, ref.T, ref.H, ref.W, ref.C) or t.buf.device != ref.buf.device):
+        raise MspiError("%s: %s [%d,%d,%d,%d,%d] must match [%d,%d,%d,%d,%d] on %s"
+                        % (name, what, t.N, t.T, t.H, t.W, t.C, ref.N, ref.T, ref.H, ref.W, ref.C, ref.buf.device))
+
+
+def _x3d_mat(name, what, t, shape, dev):
+    if t.dtype != torch.float32 or t.numel() != shape[0] * shape[1] or t.device != dev or not t.is_contiguous():
+        raise MspiError("%s: %s must be a contiguous fp32 tensor of %d x %d elements on %s, got %s %s on %s"
+                        % (name, what, shape[0], shape[1], dev, t.dtype, tuple(t.shape), t.device))
+    return t.data_ptr()
+
+
+def dwconv3_wgrad(x, dy, bias=False):
+    """Weight (and with bias=True bias) gradient of a depthwise (3,3,3) conv, padding (1,1,1), stride 1, for the output gradient
+    dy (mspi_dwconv3_wgrad); x and dy are read where they lie (channel slices of wider buffers).  Returns (dW [C,1,3,3,3], db [C]
+    or None)."""
+    lib = _lib.load()
+    _x3d_rows("dwconv3_wgrad", "x", x)
+    _x3d_rows("dwconv3_wgrad", "dy", dy, x)
+    d = _dw_desc(x, (3, 3, 3), (1, 1, 1), (1, 1, 1), dy.ld)
+    if not lib.mspi_dwconv3_wgrad_supported(C.byref(d)):
+        raise MspiError("dwconv3_wgrad: %s" % lib.mspi_last_error().decode("utf-8", "replace"))
+    dev = x.buf.device
+    dW = torch.empty(x.C, 1, 3, 3, 3, dtype=torch.float32, device=dev)
+    db = torch.empty(x.C, dtype=torch.float32, device=dev) if bias else None
+    ws = torch.empty(lib.mspi_dwconv3_wgrad_ws_bytes(C.byref(d)) // 4, dtype=torch.float32, device=dev)     # stream-ordered
+    with _Timed("dwconv3_wgrad", 54.0 * x.M * x.C, 8.0 * x.M * x.C, "in=%s C=%d" % ((x.N, x.T, x.H, x.W), x.C)):
+        check(lib.mspi_dwconv3_wgrad(C.byref(d), x.ptr, dy.ptr, dW.data_ptr(), db.data_ptr() if bias else None, ws.data_ptr(),
+                                     _stream()), "mspi_dwconv3_wgrad")
+    return dW, db
+
+
+def bn_gate_act(x, mean, rstd, gamma, beta, gate=None, res=None, act=ACT_NONE, out=None):
+    """y = act(res + gate (gamma (x - mean) rstd + beta)) in one pass (mspi_bn_gate_act_fwd): gate fp32 [N, C] per sample or
+    None, res a CL like x or None, act ACT_RELU, ACT_SWISH or ACT_NONE.  Returns a CL like x (a new one, or out)."""
+    lib = _lib.load()
+    _x3d_rows("bn_gate_act", "x", x)
+    dev = x.buf.device
+    if act not in (ACT_NONE, ACT_RELU, ACT_SWISH):
+        raise MspiError("bn_gate_act: act must be ACT_NONE, ACT_RELU or ACT_SWISH, got %s" % (act,))
+    ptrs = [_bn_vec("bn_gate_act", n, t, x.C, dev) for n, t in (("mean", mean), ("rstd", rstd), ("gamma", gamma), ("beta", beta))]
+    gp = None if gate is None else _x3d_mat("bn_gate_act", "gate", gate, (x.N, x.C), dev)
+    if res is not None:
+        _x3d_rows("bn_gate_act", "res", res, x)
+    if out is None:
+        out = alloc(x.N, x.T, x.H, x.W, x.C, dev)
+    else:
+        _x3d_rows("bn_gate_act", "out", out, x)
+    with _Timed("bn_gate_act", 6.0 * x.M * x.C, 4.0 * x.M * x.C * (2 if res is None else 3), "M=%d C=%d" % (x.M, x.C)):
+        check(lib.mspi_bn_gate_act_fwd(x.ptr, x.ld, ptrs[0], ptrs[1], ptrs[2], ptrs[3], gp, None if res is None else res.ptr,
+                                       0 if res is None else res.ld, out.ptr, out.ld, x.M, x.T * x.H * x.W, x.C, act, _stream()),
+              "mspi_bn_gate_act_fwd")
+    return out
+
+
+def gate_swish_bwd(ds, v0, mean, rstd, gamma, beta, gate=None, inplace=False):
+    """Backward of s = swish(gate bn(v0)) for the gradient ds (mspi_gate_swish_bwd), the norm, the product and the sigmoid
+    computed again from the pre-norm v0.  Returns (dv, dgate): a CL like v0 (over ds with inplace=True) and fp32 [N, C], None
+    without a gate."""
+    lib = _lib.load()
+    _x3d_rows("gate_swish_bwd", "v0", v0)
+    _x3d_rows("gate_swish_bwd", "ds", ds, v0)
+    dev = v0.buf.device
+    N, R, Cc = v0.N, v0.T * v0.H * v0.W, v0.C
+    ptrs = [_bn_vec("gate_swish_bwd", n, t, Cc, dev) for n, t in (("mean", mean), ("rstd", rstd), ("gamma", gamma), ("beta", beta))]
+    gp = None if gate is None else _x3d_mat("gate_swish_bwd", "gate", gate, (N, Cc), dev)
+    if N >= 65536:
+        raise MspiError("gate_swish_bwd: %d samples, fewer than 65536" % N)
+    dv = ds if inplace else alloc(v0.N, v0.T, v0.H, v0.W, Cc, dev)
+    dgate = ws = None
+    if gate is not None:
+        dgate = torch.empty(N, Cc, dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.mspi_gate_swish_bwd_ws_bytes(N, R, Cc) // 4, dtype=torch.float32, device=dev)  # stream-ordered
+    with _Timed("gate_swish_bwd", 20.0 * v0.M * Cc, 12.0 * v0.M * Cc, "N=%d R=%d C=%d" % (N, R, Cc)):
+        check(lib.mspi_gate_swish_bwd(ds.ptr, ds.ld, v0.ptr, v0.ld, ptrs[0], ptrs[1], ptrs[2], ptrs[3], gp, dv.ptr, dv.ld,
+                                      None if gate is None else dgate.data_ptr(), None if gate is None else ws.data_ptr(), N, R, Cc,
+                                      _stream()), "mspi_gate_swish_bwd")
+    return dv, dgate
+
+
+def _se_dims(name, pool, b1):
+    _need_gpu(pool)
+    if pool.dim() != 2 or pool.dtype != torch.float32 or not pool.is_contiguous():
+        raise MspiError("%s: the rows must be contiguous fp32 [N, C], got %s %s" % (name, pool.dtype, tuple(pool.shape)))
+    N, Cc, F = pool.shape[0], pool.shape[1], b1
+    if not 0 < N < 65536 or Cc % 4 or not 0 < Cc <= X3D_TRAIN_MAX_CH or not 0 < F <= SE_TRAIN_MAX_F:
+        raise MspiError("%s: N=%d C=%d F=%d: fewer than 65536 samples, C a multiple of 4 up to %d, fc1.out_channels F up to %d"
+                        % (name, N, Cc, F, X3D_TRAIN_MAX_CH, SE_TRAIN_MAX_F))
+    return N, Cc, F
+
+
+def se_train_fwd(pool0, mean, rstd, gamma, beta, w1, b1, w2, b2):
+    """The squeeze-excite MLP behind a BatchNorm on batch statistics (mspi_se_train_fwd): pool0 fp32 [N, C] = mean_rows of the
+    pre-norm map, w1 [F,C,1,1,1], b1 [F], w2 [C,F,1,1,1], b2 [C] contiguous fp32.  Returns (p [N, C], h [N, F], gate [N, C])."""
+    lib = _lib.load()
+    N, Cc, F = _se_dims("se_train_fwd", pool0, b1.numel())
+    dev = pool0.device
+    vec = [_bn_vec("se_train_fwd", n, t, Cc, dev) for n, t in (("mean", mean), ("rstd", rstd), ("gamma", gamma), ("beta", beta))]
+    pw1, pw2 = _x3d_mat("se_train_fwd", "fc1.weight", w1, (F, Cc), dev), _x3d_mat("se_train_fwd", "fc2.weight", w2, (Cc, F), dev)
+    pb1, pb2 = _bn_vec("se_train_fwd", "fc1.bias", b1, F, dev), _bn_vec("se_train_fwd", "fc2.bias", b2, Cc, dev)
+    p, gate = (torch.empty(N, Cc, dtype=torch.float32, device=dev) for _ in range(2))
+    h = torch.empty(N, F, dtype=torch.float32, device=dev)
+    with _Timed("se_train_fwd", 4.0 * N * Cc * F, 8.0 * Cc * F, "N=%d C=%d F=%d" % (N, Cc, F)):
+        check(lib.mspi_se_train_fwd(pool0.data_ptr(), vec[0], vec[1], vec[2], vec[3], pw1, pb1, pw2, pb2, p.data_ptr(), h.data_ptr(),
+                                    gate.data_ptr(), N, Cc, F, _stream()), "mspi_se_train_fwd")
+    return p, h, gate
+
+
+def se_train_bwd(dgate, gate, h, p, w1, w2):
+    """Backward of se_train_fwd from dgate [N, C] with the forward's p, h and gate (mspi_se_train_bwd), the samples added in index
+    order.  Returns (dw1 [F,C,1,1,1], db1 [F], dw2 [C,F,1,1,1], db2 [C], dp [N, C]); mean_rows_bwd(dp, dv, accumulate=True) is
+    the caller's."""
+    lib = _lib.load()
+    N, Cc, F = _se_dims("se_train_bwd", dgate, h.shape[-1] if h.dim() == 2 else 0)
+    dev = dgate.device
+    pg, pp = _x3d_mat("se_train_bwd", "gate", gate, (N, Cc), dev), _x3d_mat("se_train_bwd", "p", p, (N, Cc), dev)
+    ph = _x3d_mat("se_train_bwd", "h", h, (N, F), dev)
+    pw1, pw2 = _x3d_mat("se_train_bwd", "fc1.weight", w1, (F, Cc), dev), _x3d_mat("se_train_bwd", "fc2.weight", w2, (Cc, F), dev)
+    dw1 = torch.empty(F, Cc, 1, 1, 1, dtype=torch.float32, device=dev)
+    dw2 = torch.empty(Cc, F, 1, 1, 1, dtype=torch.float32, device=dev)
+    db1, db2 = torch.empty(F, dtype=torch.float32, device=dev), torch.empty(Cc, dtype=torch.float32, device=dev)
+    dp = torch.empty(N, Cc, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.mspi_se_train_bwd_ws_bytes(N, Cc, F) // 4, dtype=torch.float32, device=dev)        # stream-ordered
+    with _Timed("se_train_bwd", 8.0 * N * Cc * F, 16.0 * Cc * F, "N=%d C=%d F=%d" % (N, Cc, F)):
+        check(lib.mspi_se_train_bwd(dgate.data_ptr(), pg, ph, pp, pw1, pw2, dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(),
+                                    db2.data_ptr(), dp.data_ptr(), ws.data_ptr(), N, Cc, F, _stream()), "mspi_se_train_bwd")
+    return dw1, db1, dw2, db2, dp
+
+
+def relu_mask_add(dx, g, y):
+    """dx += g where y > 0 (mspi_relu_mask_add): the skip path of y = relu(x + f(x)).  Returns dx."""
+    lib = _lib.load()
+    _need_gpu(dx.buf)
+    for what, t in (("dx", dx), ("g", g), ("y", y)):
+        if not t.dense or t.Cs != t.C or (t.M, t.C) != (dx.M, dx.C) or t.buf.device != dx.buf.device:
+            raise MspiError("relu_mask_add: %s must be dense rows, a multiple of 4 wide, like dx (%d rows x %d on %s)"
+                            % (what, dx.M, dx.C, dx.buf.device))
+    with _Timed("relu_mask_add", 1.0 * dx.M * dx.C, 16.0 * dx.M * dx.C, "M=%d C=%d" % (dx.M, dx.C)):
+        check(lib.mspi_relu_mask_add(dx.ptr, dx.ld, g.ptr, g.ld, y.ptr, y.ld, dx.M, dx.C, _stream()), "mspi_relu_mask_add")
     return dx
 
 
